@@ -14,9 +14,14 @@ random (TF1 glorot) init.  Weak scaling: per-GPU batch fixed at 100, so the glob
 is 100*W.  A timed step is the full worker step: batch fetch, forward, backward,
 gradient push (RCCL), PS Adam update, parameter pull — eval excluded.
 
-Usage:  python bench.py [--gpus N --steps K --warmup W]
+Usage:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   N>1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
             --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full`` adds
+everything else the benchmark measures: the test accuracy after the run, the extra shard plans
+(W > 1) and the time-to-accuracy runs.  ``--dump-outputs DIR`` writes what the last timed step
+left with its caller (parameters, gradients, loss) as ``DIR/<name>.npy``.
 """
 from __future__ import annotations
 
@@ -85,8 +90,18 @@ def main(argv=None):
     ap.add_argument("--ab-steps", type=int, default=30,
                     help="timed steps per candidate of the --exchange auto A/B")
     ap.add_argument("--splits", default=None, help="comma-separated split-K factors per op")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beyond the headline "
+                         "figure: the test accuracy after the run, the --extra-plans (W > 1) and "
+                         "the time-to-accuracy runs (--tta); off by default")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step left with its "
+                         "caller as DIR/<name>.npy (float32): params (the updated flat parameter "
+                         "buffer), grads (the step's flat gradient buffer) and, with the HIP "
+                         "engine, loss (mean loss of the step's batch, one element).  Same arguments, "
+                         "same inputs: init, data and dropout seeds are fixed")
     ap.add_argument("--tta", type=float, default=0.95,
-                    help="after the throughput run, train one reference epoch (500 steps/worker, "
+                    help="with --full: after the throughput run, train one reference epoch (500 steps/worker, "
                          "full test-set eval every 10 steps, eval time included) and report the "
                          "wall time to this test accuracy; <= 0 skips it")
     ap.add_argument("--tta-steps", type=int, default=None,
@@ -106,7 +121,7 @@ def main(argv=None):
                          "alternating rounds: prewarm 100 0.2967-0.2979, 300 0.2958-0.3012, 1000 "
                          "0.2955-0.2965 ms/step (profiles/r5_driver_window_prewarm.txt)")
     ap.add_argument("--extra-plans", default="contiguous",
-                    help="W > 1 sync: comma-separated shard plans also timed after the headline "
+                    help="with --full, W > 1 sync: comma-separated shard plans also timed after the headline "
                          "plan (same steps), reported under 'plans' (BASELINE config 3 names "
                          "contiguous shards); empty string skips them")
     a = ap.parse_args(argv)
@@ -323,13 +338,23 @@ def main(argv=None):
     elapsed = timed_run(tr)
     ms = 1e3 * elapsed / a.steps
     imgs = world * a.batch_size * a.steps / elapsed
-    acc = tr.evaluate()
+    if a.dump_outputs and env.rank == 0:
+        # what the last timed step left with its caller (sync replicas are equal on every rank)
+        import numpy as np
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        outs = {"params": tr.params, "grads": tr.grads}
+        if hasattr(tr.engine, "loss"):
+            outs["loss"] = tr.engine.loss().reshape(1)
+        for name, t in outs.items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"),
+                    t.detach().to("cpu", torch.float32).numpy())
+    acc = tr.evaluate() if a.full else None
 
     # W > 1 sync: the reference's tensor-granular plans on the same harness (RCCL grouped
     # reduce / broadcast; contiguous puts 59 % of the bytes on the last PS at W = 8)
     plans = {}
     extra = [p for p in a.extra_plans.split(",") if p and p != a.shard]
-    if world > 1 and a.mode == "sync" and extra:
+    if a.full and world > 1 and a.mode == "sync" and extra:
         # each plan over RCCL (grouped reduce / broadcast) and over the xGMI owner buckets (one
         # push / owner update / pull kernel per unit); a shared-GPU rehearsal has no RCCL
         for p in extra:
@@ -403,7 +428,7 @@ def main(argv=None):
     # ... and on the hard synthetic set (the default set ends its epoch at
     # 0.998, too easy to show what staleness or the replicate protocol cost in convergence)
     tta, tta_rep, tta_hard, tta_hard_rep = None, None, None, None
-    if a.tta is not None and a.tta > 0:
+    if a.full and a.tta is not None and a.tta > 0:
         tta = time_to_acc("stride")
         if world > 1:
             tta_rep = time_to_acc("replicate")
@@ -447,12 +472,13 @@ def main(argv=None):
                             else "n/a (W = 1, local updates)" if world == 1
                             else "n/a (no native runner)"),
             },
-            "test_acc_after_run": round(acc, 4),
             "prewarm": {"steps": n_pre, "note": "untimed steps before the warmup steps: the "
                         "GPU is still ramping up after a few steps (20-step window after 5 "
                         "warmup steps: 0.322 vs 0.308 ms/step after 100; after 1000 the "
                         "20-step window spreads 1 us instead of 1-5 us)"},
         }
+        if acc is not None:
+            rec["test_acc_after_run"] = round(acc, 4)
         if handoff:
             rec["handoff_check"] = handoff
         if replica_check is not None:

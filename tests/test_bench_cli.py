@@ -48,10 +48,35 @@ def test_bench_single_process_json():
 
 
 @pytest.mark.slow
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the run stops after the timed steps (no accuracy, plans or time-to-accuracy
+    fields although --tta keeps its default), and --dump-outputs writes the last step's
+    parameters and gradients as float32 .npy files that a second run reproduces bit for bit."""
+    import numpy as np
+    dumps = []
+    for d in ("a", "b"):
+        out = tmp_path / d
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup",
+                            "1", "--dump-outputs", str(out)],
+                           cwd=ROOT, capture_output=True, text=True, timeout=600, env=_env())
+        assert r.returncode == 0, r.stderr[-2000:]
+        recs = _json_lines(r.stdout)
+        assert len(recs) == 1
+        assert KEYS <= recs[0].keys() and recs[0]["steps"] == 2
+        assert not {"test_acc_after_run", "plans", "time_to_acc", "time_to_acc_hard"} & recs[0].keys()
+        dumps.append({n: np.load(out / f"{n}.npy") for n in ("params", "grads")})
+    for n, a in dumps[0].items():
+        assert a.dtype == np.float32 and a.ndim == 1 and a.size >= 2656010
+        assert np.isfinite(a).all() and np.abs(a).sum() > 0
+        assert np.array_equal(a, dumps[1][n]), n
+    assert sum(a.nbytes for a in dumps[0].values()) <= 64 << 20
+
+
+@pytest.mark.slow
 def test_bench_torchrun_two_ranks_json(port):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2",
-           "--steps", "2", "--warmup", "1", "--tta", "0.99", "--tta-steps", "2"]
+           "--steps", "2", "--warmup", "1", "--full", "--tta", "0.99", "--tta-steps", "2"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=_env())
     assert r.returncode == 0, r.stderr[-2000:]
     recs = _json_lines(r.stdout)
