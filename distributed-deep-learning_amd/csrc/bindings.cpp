@@ -87,9 +87,10 @@ class PyEngine {
     for (int i = 0; i < ddl::OP_COUNT; ++i) {
       // the eval-only large tiles exist for the conv2-4 forward ops only
       const bool big = i == ddl::OP_CONV2_FWD || i == ddl::OP_CONV3_FWD || i == ddl::OP_CONV4_FWD;
-      // (CFG_KWAVE: the K-wave launch; ops without a K-wave instantiation fall back to the
+      // (CFG_KWAVE / CFG_MF16 / CFG_KW16 — the engine's own defaults hold the latter two, so
+      // get_eval_cfg's list can be set back; ops without an instantiation of one fall back to the
       // one-wave 32x32 tile, engine_impl.h launch_cfg)
-      TORCH_CHECK(c[i] == ddl::CFG_KWAVE ||
+      TORCH_CHECK(c[i] == ddl::CFG_KWAVE || c[i] == ddl::CFG_MF16 || c[i] == ddl::CFG_KW16 ||
                       (c[i] >= 0 && c[i] < (big ? ddl::NUM_EVAL_TILE_CFGS : ddl::NUM_TILE_CFGS)),
                   "tile config out of range");
       e_.eval_cfg[i] = (int)c[i];

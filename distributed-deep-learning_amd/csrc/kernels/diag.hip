@@ -75,6 +75,7 @@ void launch_gemm_nomem(float* out, int M, int N, int K, int splits, void* slab, 
   NoMemPolicy p{M, N, K, out};
   SplitScratch sc;
   sc.slab = slab;
+  sc.slab_f4 = (size_t)-1;  // sized by the caller
   sc.tickets = tickets;
   launch_gemm<32, 32, 32, 1, 1>(p, splits, 1, sc, st);
 }

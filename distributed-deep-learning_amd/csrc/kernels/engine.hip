@@ -147,14 +147,20 @@ static size_t slab_need(int c, int M, int N, int K, int s) {
   }
 }
 
+// Largest slab any op needs at any batch up to B.  Not just at B: a split count is K over the
+// chunk rounded up to whole K tiles, so it is not monotonic in the batch (conv4's weight
+// gradient, split 6: 5 partials at batch 40, 6 at batch 33 and at every batch <= 32, where the
+// batch-minor K is padded to 32 images), and a smaller batch on the same engine — a last
+// partial batch, a test — would write its extra partials past the slab.
 size_t Engine::slab_floats_needed(int B) const {
   size_t mx = 0;
-  for (int op = 0; op < OP_COUNT; ++op) {
-    int M, N, K;
-    op_shape(op, B, &M, &N, &K);
-    const size_t f = 4 * slab_need(cfg[op], M, N, K, splits[op]);
-    if (f > mx) mx = f;
-  }
+  for (int b = 1; b <= B; ++b)
+    for (int op = 0; op < OP_COUNT; ++op) {
+      int M, N, K;
+      op_shape(op, b, &M, &N, &K);
+      const size_t f = 4 * slab_need(cfg[op], M, N, K, splits[op]);
+      if (f > mx) mx = f;
+    }
   return mx;
 }
 

@@ -36,6 +36,7 @@
 //   mode 2: partials only; splitk_wide_reduce sums them with RL lanes per output element
 //     and runs the epilogue.
 #pragma once
+#include <stdexcept>
 #include <stdlib.h>
 
 #include <type_traits>
@@ -1519,6 +1520,11 @@ inline SubGrid plan_gemm(const P& p, int splits, int wide_thr, const SplitScratc
   g.kchunk = g.gz > 1 ? splitk_kchunk<BK>(p.K, splits) : p.K;
   g.mode = g.gz == 1 ? 0 : (g.gz > wide_thr ? 2 : 1);
   if (g.mode == 1 && (long long)g.gx * g.gy > sc.max_tiles) g.mode = 2;  // ticket capacity
+  // the gz partial tiles (BM * BN / 4 float4 each, TileGeo::PART4) must fit the slab: the split
+  // count comes from K, and K's rounding to whole tiles can give a smaller batch one more split
+  // than the batch the slab was sized for
+  if (g.mode != 0 && (size_t)g.gz * g.gx * g.gy * (size_t)(BM * BN / 4) > sc.slab_f4)
+    throw std::runtime_error("split-K partials exceed the scratch slab");
   g.nblocks = g.gx * g.gy * g.gz;
   return g;
 }

@@ -499,6 +499,30 @@ def test_adam_kernel(n, off):
     assert (W[off:].cpu() - w2).abs().max() < 1e-6
 
 
+@pytest.mark.parametrize("scale", [1.0, 0.5])
+@pytest.mark.parametrize("mu", [0.9, 0.0])
+@pytest.mark.parametrize("n,off", [(4096, 0), (1000, 3), (4098, 4), (2656010, 0)])
+def test_momentum_kernel(n, off, mu, scale):
+    """momentum_flat (momentum / plain-SGD optimizers, mu = 0: plain SGD) against the fp64 closed
+    form of common.h momentum1, m' = mu m + scale g, w' = w - lr m' (what parallel/ps.py
+    expects), at the sizes, misalignments and bounds of test_adam_kernel."""
+    from ddl_amd.ops import native
+    torch.manual_seed(2)
+    w = torch.randn(n + off)
+    g = torch.randn(n + off) * 1e-2
+    m = torch.randn(n + off) * 1e-3
+    lr = 3e-2
+    W, G, M = (t.to(DEV) for t in (w, g, m))
+    native.ops().momentum_flat(W[off:], G[off:], M[off:], lr, mu, scale)
+    m2 = m[off:].double() * mu + g[off:].double() * scale
+    w2 = w[off:].double() - lr * m2
+    assert rel_err(M[off:], m2) < 1e-6
+    assert (W[off:].cpu().double() - w2).abs().max() < 1e-6
+    # the gradient is read only, and nothing in front of the shard is touched
+    assert torch.equal(G.cpu(), g)
+    assert torch.equal(W[:off].cpu(), w[:off]) and torch.equal(M[:off].cpu(), m[:off])
+
+
 def test_training_tracks_torch_engine():
     """20 Adam steps: HIP engine vs stock-torch engine on the same GPU stay close and
     both reduce the loss."""

@@ -1,0 +1,172 @@
+"""The per-op references of tests/op_reference.py, checked on the CPU: chained into a full step
+they reproduce fp64 autograd; the integer data of the exact GPU tests satisfies the exactness
+condition; and the real-valued metric notices one extra typical term in one output element."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+import op_reference as R
+from ddl_amd.models.layout import CANON_OFFSETS, TOTAL_NUMEL
+from ddl_amd.models.mnist_cnn import (torch_forward, xent_loss, dropout_apply, init_params_,
+                                      param_views)
+
+BATCHES = (1, 5, 33)   # the batches of tests/test_op_oracle_gpu.py
+
+
+def relerr(a, b):
+    a, b = a.double(), b.double()
+    return float((a - b).abs().max() / (b.abs().max() + 1e-300))
+
+
+def autograd_step(P, x, y, keep, seed):
+    """mnist_cnn.torch_forward op by op in fp64, keeping every intermediate and its gradient."""
+    pv = [p.double().clone().requires_grad_(True) for p in P]
+    n = x.shape[0]
+    h = x.double().view(n, 1, 28, 28)
+    pres, pooled, codes = [], [], []
+    for li in range(4):
+        pre = F.conv2d(h, pv[2 * li].permute(3, 2, 0, 1), pv[2 * li + 1], padding=2)
+        pre.retain_grad()
+        r = F.relu(pre)
+        if r.shape[-1] % 2:
+            r = F.pad(r, (0, 1, 0, 1), value=float("-inf"))
+        wp = r.shape[-1]
+        h, idx = F.max_pool2d(r, 2, 2, return_indices=True)
+        hp = h.shape[-1]
+        iy, ix = idx // wp, idx % wp
+        py = torch.arange(hp).view(1, 1, hp, 1)
+        px = torch.arange(hp).view(1, 1, 1, hp)
+        q = (iy - 2 * py) * 2 + (ix - 2 * px)
+        code = torch.where(h > 0, q, torch.full_like(q, R.NO_GRAD_CODE))
+        pres.append(pre)
+        pooled.append(h.permute(0, 2, 3, 1))
+        codes.append(code.permute(0, 2, 3, 1).to(torch.uint8))
+    f = h.permute(0, 2, 3, 1).reshape(n, -1)
+    a1 = f @ pv[8] + pv[9]
+    a1.retain_grad()
+    h1 = dropout_apply(F.relu(a1), seed, 1, keep)
+    a2 = h1 @ pv[10] + pv[11]
+    a2.retain_grad()
+    h2 = dropout_apply(a2, seed, 2, keep)
+    logits = h2 @ pv[12] + pv[13]
+    logits.retain_grad()
+    with torch.no_grad():
+        assert torch.equal(logits, torch_forward([p.double() for p in P], x.double(), keep, seed))
+    rows = F.cross_entropy(logits, y, reduction="none")
+    xent_loss(logits, y).backward()
+    inter = {"h1": h1, "h2": h2, "loss": rows, "dlog": logits.grad, "dpre2fc": a2.grad,
+             "dpre1fc": a1.grad}
+    for li in range(4):
+        inter[f"p{li + 1}"] = pooled[li]
+        inter[f"c{li + 1}"] = codes[li]
+        inter[f"d{li + 1}"] = pres[li].grad.permute(0, 2, 3, 1)
+    return {k: v.detach() for k, v in inter.items()}, [p.grad for p in pv]
+
+
+def reference_step(P, x, y, keep, seed):
+    """The per-op references chained in the engine's op order (api.h `enum Op`)."""
+    buf = {"x": x}
+    for op in range(6):
+        buf.update(R.run_op(op, P, buf, seed, keep))
+    B = x.shape[0]
+    m2 = R.keep_mask(seed, 2, B, 512, keep) if keep < 1.0 else None
+    hd = R.head(buf["h2"], P[12], P[13], y, m2, 1.0 / keep)
+    buf.update(loss=hd["loss"], dlog=hd["dlog"], dpre2fc=hd["dpre2fc"], g12=hd["gw"], g13=hd["gb"])
+    for op in range(6, R.OP_COUNT):
+        buf.update(R.run_op(op, P, buf, seed, keep))
+    return buf
+
+
+@pytest.mark.parametrize("keep", [0.5, 1.0])
+def test_reference_chain_matches_autograd(keep):
+    torch.manual_seed(5)
+    B, seed = 3, 321
+    flat = torch.zeros(TOTAL_NUMEL)
+    init_params_(flat, CANON_OFFSETS, seed=7)
+    P = [p.double() + (0.05 * torch.randn(p.shape) if p.dim() == 1 else 0)
+         for p in param_views(flat, CANON_OFFSETS)]
+    x = torch.rand(B, 784, dtype=torch.float64) * 1.5 - 0.5
+    y = torch.tensor([9, 0, 4])
+    want, wgrads = autograd_step(P, x, y, keep, seed)
+    got = reference_step(P, x, y, keep, seed)
+    for i in range(14):
+        assert got[f"g{i}"].shape == wgrads[i].shape, i
+        assert relerr(got[f"g{i}"], wgrads[i]) < 1e-12, f"g{i}"
+        assert wgrads[i].abs().max() > 0, i
+    for name, ref in want.items():
+        g = got[name].reshape(ref.shape)
+        if name.startswith("c"):
+            assert torch.equal(g, ref), name
+            u = torch.unique(ref).tolist()
+            assert R.NO_GRAD_CODE in u and len(u) >= 4, (name, u)   # positions and 0xFF occur
+        else:
+            assert relerr(g, ref) < 1e-12, name
+            assert ref.abs().max() > 0, name
+
+
+def test_exactness_condition():
+    """K_terms * amax^2 < 2^24 for every op and batch of the exact GPU tests: every product and
+    partial sum of small integers is an fp32 integer, so any summation order gives the same bits."""
+    worst = (0, None)
+    P = R.make_params(1)
+    assert all(float(p.abs().max()) <= R.INT_AMAX and torch.equal(p, p.round()) for p in P)
+    assert all(bool((p != 0).all()) for p in P[1::2])   # non-zero biases
+    for B in BATCHES:
+        for op in range(R.OP_COUNT):
+            k = R.k_terms(op, B)
+            assert k * R.INT_AMAX ** 2 < 2 ** 24, (R.OP_NAMES[op], B)
+            worst = max(worst, (k, (R.OP_NAMES[op], B)))
+            for name, v in R.make_inputs(op, B, 1).items():
+                if v.dtype != torch.uint8:
+                    assert float(v.abs().max()) <= R.INT_AMAX and torch.equal(v, v.round()), name
+                    assert 0.3 < float((v == 0).float().mean()) < 0.75, name   # sparse
+                    assert float(v.sum()) != 0, name
+    assert worst == (25872, ("conv1_wgrad", 33))
+    # dropout and its backward scale by 1 / keep = 2: still exact
+    assert 2 * 1025 * R.INT_AMAX ** 2 < 2 ** 24
+
+
+def operands(op, P, buf):
+    fl = [buf[n] for n in R.OP_IO[op][0] if buf[n].dtype != torch.uint8]
+    if op == 6:
+        fl = [buf["dpre2fc"]]   # h1 is only fc2's mask there
+    return fl + ([P[R.OP_WEIGHT[op]]] if op in R.OP_WEIGHT else [])
+
+
+@pytest.mark.parametrize("op", range(R.OP_COUNT))
+def test_metric_notices_one_term(op):
+    """Sensitivity of the real-valued check (tests/test_op_oracle_gpu.py) at the op's largest K
+    (B = 33): the fp32 CPU result passes; the same result with one typical term (the median
+    |a_i b_i|) added to one output element — the one with the largest abs-sum, where a term is
+    smallest against the bound — fails."""
+    B, keep, seed = 33, 0.5, 77
+    P = R.make_params(3, real=True)
+    buf = R.make_inputs(op, B, 3, real=True)
+    ref = R.run_op(op, P, buf, seed, keep)
+    f32 = R.run_op(op, P, buf, seed, keep, dtype=torch.float32)
+    asum = R.abs_sum(op, P, buf, keep)
+    a, b = operands(op, P, buf)
+    gen = torch.Generator().manual_seed(op)
+    ia = torch.randint(0, a.numel(), (100000,), generator=gen)
+    ib = torch.randint(0, b.numel(), (100000,), generator=gen)
+    term = float((a.reshape(-1)[ia] * b.reshape(-1)[ib]).abs().median())
+    assert term > 0
+    K = R.k_terms(op, B)
+    for name, s in asum.items():
+        r64, g32 = ref[name], f32[name]
+        assert g32.dtype == torch.float32
+        base = R.rms(R.rel_err(g32, r64, s)[0], s)
+        fails, _ = R.precision_failures(g32, r64, s, K, base)
+        assert not fails, (name, fails)
+        bad = g32.clone()
+        if name in ("g1", "g3", "g5", "g7", "g9", "g11"):
+            # a bias gradient sums one operand only: its typical term is the median |dy|
+            t = float(b.abs().median())
+        else:
+            t = term
+        i = int(s.reshape(-1).argmax())
+        bad.view(-1)[i] += t
+        fails, m = R.precision_failures(bad, r64, s, K, base)
+        print(f"{R.OP_NAMES[op]} {name}: K={K} fp32 rms {base:.3g}, with one term rms {m[1]:.3g} "
+              f"max {m[0]:.3g} (ceiling {(K + 8) * R.U32:.3g})")
+        assert fails, (name, t)
