@@ -665,6 +665,7 @@ class PyRunner {
   void set_use_tail(bool on) { r_->set_use_tail(on); }
   void set_final_in_reduce(bool on) { r_->set_final_in_reduce(on); }
   void set_tail_cfg(int64_t first, int64_t f4) { r_->set_tail_cfg((int)first, (int)f4); }
+  int64_t update_launches() const { return r_->update_launches(); }
   void step(at::Tensor x, at::Tensor labels, int64_t seed, std::vector<double> lr_t) {
     eng_.check_batch(x);
     TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_cuda(), "labels must be int64 GPU");
@@ -811,6 +812,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("set_use_tail", &PyRunner::set_use_tail)
       .def("set_ready_flags", &PyRunner::set_ready_flags)
       .def("set_final_in_reduce", &PyRunner::set_final_in_reduce)
+      .def("update_launches", &PyRunner::update_launches,
+           "Stand-alone optimizer kernel launches issued for the most recent step()")
       .def("set_tail_cfg", &PyRunner::set_tail_cfg)
       .def("step", &PyRunner::step)
       .def("selftest", &PyRunner::selftest)

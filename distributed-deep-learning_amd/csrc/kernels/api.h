@@ -31,8 +31,9 @@ void launch_adam(float* w, const float* g, float* m, float* v, int64_t n, float 
 // same with c1 = 1 - beta1, c2 = 1 - beta2 precomputed (bit-identical to launch_adam)
 void launch_adam_c(float* w, const float* g, float* m, float* v, int64_t n, float lr_t, float c1,
                    float c2, float eps, float scale, hipStream_t st, int max_grid = 2048);
+// 16-B vector kernel when w, g and m are 16-B aligned, else the scalar one (bit-identical)
 void launch_momentum(float* w, const float* g, float* m, int64_t n, float lr, float mu,
-                     float scale, hipStream_t st);
+                     float scale, hipStream_t st, int max_grid = 2048);
 void launch_scale(float* p, int64_t n, float a, hipStream_t st);
 
 // ---- conv1 forward as a direct LDS-staged kernel (conv1.hip) --------------------------------
@@ -150,6 +151,9 @@ struct Engine {
   // reduce epilogue, the rest as tail blocks of that launch (engine_impl.h dual_then_b).
   // Cleared when taken; the runner launches it as before when it is still pending.
   UpdTail final_upd;
+  // stand-alone optimizer launches flush_tail() has issued for update tails no launch took
+  // (host counter, diagnostic: SyncRunner::update_launches)
+  int update_launches = 0;
   // eval forward: conv2 on the tap-skipping K map (DDL_EVAL_KMAP2=0: the image-major GEMM)
   bool eval_kmap2 = [] {
     const char* e = getenv("DDL_EVAL_KMAP2");
@@ -662,6 +666,10 @@ class SyncRunner {
   // orderly ncclCommDestroy (call on every rank at the same point), then release()
   void close();
   hipStream_t comm_stream() const { return cs_; }
+  // stand-alone optimizer kernel launches (update / gradient scale / a flushed update tail)
+  // issued for the most recent step(): 0 when every update rode in a backward launch.  Counted
+  // on the host; diagnostic only
+  int update_launches() const { return upd_launches_ + eng_->update_launches; }
 
  private:
   void issue(const RunnerUnit& u, const float* lr_t, hipStream_t st);
@@ -671,6 +679,8 @@ class SyncRunner {
                           hipStream_t st);
   void update(float* w, const float* g, float* m, float* v, int64_t n, float lr_t,
               hipStream_t st);
+  void scale_grads(float* p, int64_t n, hipStream_t st);  // g *= coef_
+  int upd_launches_ = 0;
   void issue_xgmi(const RunnerUnit& u, const float* lr_t, bool final_wait, hipStream_t st,
                   bool gated = false);
   int last_xgmi_ = -1;     // index of the step's last XGMI unit (carries the final wait)
@@ -723,6 +733,7 @@ class SyncRunner {
   // shaped (tail_ok_), the last segment's is launched after the backward
   std::vector<Piece> seg_pieces_[kSegments];
   bool tail_ok_ = false;
+  bool tail_v_ok_ = false;  // ... and has a 16-B aligned v (the Adam rule; momentum has none)
   bool use_tail_ = true;
   bool final_in_reduce_ = [] {
     const char* e = getenv("DDL_FINAL_IN_REDUCE");

@@ -34,6 +34,8 @@ struct C1Adam {
   float *b_w = nullptr, *b_m = nullptr, *b_v = nullptr;  // bias [32] spans
   float lr_t = 0.f, c1 = 0.f, c2 = 0.f, eps = 0.f, scale = 1.f;
   int on = 0;
+  int rule = kTailAdam;  // tail.h: kTailMomentum applies momentum1 (w_v / b_v null, untouched)
+  float mu = 0.f;
 };
 constexpr int kC1wElems = 26 * 32; // dW_aug[26][32] (row 25: db)
 
@@ -100,6 +102,23 @@ DDL_DEV void c1w_sum(brsrc_t part, int src, int n, brsrc_t out, int dst, float* 
   constexpr int EPT = kC1wEPT;
   float s[EPT];
   c1w_accum<U>(part, src, n, s);
+  // the momentum rule in a loop of its own, chosen once: the Adam loop below stays as it was
+  if (gw && ad && ad->on && ad->rule == kTailMomentum) {
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) {
+      const int e = (int)threadIdx.x + 256 * j;
+      if (e >= kC1wElems) continue;
+      const bool wrow = e < 25 * 32;
+      const int i = wrow ? e : e - 25 * 32;
+      (wrow ? gw : gb)[i] = s[j];
+      float* pw = wrow ? ad->w_w : ad->b_w;
+      float* pm = wrow ? ad->w_m : ad->b_m;
+      float W = pw[i], M = pm[i];
+      momentum1(W, s[j], M, ad->lr_t, ad->mu, ad->scale);
+      pw[i] = W; pm[i] = M;
+    }
+    return;
+  }
 #pragma unroll
   for (int j = 0; j < EPT; ++j) {
     const int e = (int)threadIdx.x + 256 * j;

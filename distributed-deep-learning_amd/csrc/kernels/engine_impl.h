@@ -323,6 +323,9 @@ void run_dual_inst(Engine& e, const float* x, int B, const uint32_t* seed, hipSt
 // Split the last segment's update `in` into conv1's weight / bias spans (applied by the
 // epilogue of conv1's weight-gradient reduce: `pa`) and the remaining ranges (`rest`, tail
 // blocks of that launch).  false: the layout does not allow it (the caller keeps `in`).
+// (a momentum tail's v is null: no arithmetic on it)
+inline float* span_at(float* p, int64_t off) { return p ? p + off : nullptr; }
+
 template <class PN>
 inline bool final_split(const Engine& e, const UpdTail& in, const PN& pn, WgradAdam<PN>& pa,
                         UpdTail& rest) {
@@ -337,7 +340,7 @@ inline bool final_split(const Engine& e, const UpdTail& in, const PN& pn, WgradA
     if (hi <= lo) return true;
     if ((hi - lo) % 4 || rest.npieces >= kTailPieces) return false;
     UpdPiece q = p;
-    q.w = p.w + lo; q.g = p.g + lo; q.m = p.m + lo; q.v = p.v + lo;
+    q.w = p.w + lo; q.g = p.g + lo; q.m = p.m + lo; q.v = span_at(p.v, lo);
     if (!a16(q.w) || !a16(q.g) || !a16(q.m) || !a16(q.v)) return false;
     q.n = hi - lo;
     q.blk0 = blk;
@@ -354,7 +357,7 @@ inline bool final_split(const Engine& e, const UpdTail& in, const PN& pn, WgradA
       const int64_t o = s.w - p.w;
       if (o + s.n <= 0 || o >= p.n) continue;       // disjoint
       if (o < 0 || o + s.n > p.n) return false;      // straddles the piece edge
-      s.pw = p.w + o; s.pm = p.m + o; s.pv = p.v + o; s.lr_t = p.lr_t;
+      s.pw = p.w + o; s.pm = p.m + o; s.pv = span_at(p.v, o); s.lr_t = p.lr_t;
       cuts[nc][0] = o; cuts[nc][1] = o + s.n; ++nc;
     }
     if (nc == 2 && cuts[1][0] < cuts[0][0]) {
@@ -375,17 +378,19 @@ inline bool final_split(const Engine& e, const UpdTail& in, const PN& pn, WgradA
   pa.b_w = sp[1].pw; pa.b_m = sp[1].pm; pa.b_v = sp[1].pv;
   pa.lr_t = sp[0].lr_t;
   pa.c1 = in.c1; pa.c2 = in.c2; pa.eps = in.eps; pa.scale = in.scale;
+  pa.rule = in.rule; pa.mu = in.mu;
   return true;
 }
 
-// The Adam spans (parameter, m, v, lr_t) of [w, w + n) inside the update pieces of `t`.
+// The update spans (parameter, m, v, lr_t) of [w, w + n) inside the update pieces of `t` (v null
+// under the momentum rule).
 inline bool find_span(const UpdTail& t, const float* w, int64_t n, float*& pw, float*& pm,
                       float*& pv, float& lr) {
   for (int i = 0; i < t.npieces; ++i) {
     const UpdPiece& p = t.p[i];
     const int64_t o = w - p.w;
     if (o >= 0 && o + n <= p.n) {
-      pw = p.w + o; pm = p.m + o; pv = p.v + o; lr = p.lr_t;
+      pw = p.w + o; pm = p.m + o; pv = span_at(p.v, o); lr = p.lr_t;
       return true;
     }
   }
@@ -436,6 +441,8 @@ inline bool final_split_conv12(const Engine& e, const UpdTail& in, const PB& pb,
   pa.c2 = ad.c2 = in.c2;
   pa.eps = ad.eps = in.eps;
   pa.scale = ad.scale = in.scale;
+  pa.rule = ad.rule = in.rule;
+  pa.mu = ad.mu = in.mu;
   ad.on = 1;
   return true;
 }

@@ -99,6 +99,29 @@ DDL_DEV void tail_body(const UpdTail& t, int b) {
   float4* w = reinterpret_cast<float4*>(P.w);
   const float4* g = reinterpret_cast<const float4*>(P.g);
   float4* m = reinterpret_cast<float4*>(P.m);
+  if (t.rule == kTailMomentum) {  // wave-uniform (kernel argument): w, g, m only, P.v is null
+    for (int off = 0; off < t.f4_per_block; off += kTailF4PerBlock) {
+      const int64_t base = blk_base + off;
+      if (base >= n4) break;
+      float4 W[kTailF4PerLane], G[kTailF4PerLane], M[kTailF4PerLane];
+#pragma unroll
+      for (int j = 0; j < kTailF4PerLane; ++j) {
+        const int64_t e = base + j * 64;
+        if (e < n4) { W[j] = w[e]; G[j] = g[e]; M[j] = m[e]; }
+      }
+#pragma unroll
+      for (int j = 0; j < kTailF4PerLane; ++j) {
+        const int64_t e = base + j * 64;
+        if (e >= n4) continue;
+        momentum1(W[j].x, G[j].x, M[j].x, P.lr_t, t.mu, t.scale);
+        momentum1(W[j].y, G[j].y, M[j].y, P.lr_t, t.mu, t.scale);
+        momentum1(W[j].z, G[j].z, M[j].z, P.lr_t, t.mu, t.scale);
+        momentum1(W[j].w, G[j].w, M[j].w, P.lr_t, t.mu, t.scale);
+        w[e] = W[j]; m[e] = M[j];
+      }
+    }
+    return;
+  }
   float4* v = reinterpret_cast<float4*>(P.v);
   for (int off = 0; off < t.f4_per_block; off += kTailF4PerBlock) {
     const int64_t base = blk_base + off;

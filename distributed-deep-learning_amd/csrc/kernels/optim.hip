@@ -7,6 +7,8 @@
 // lr_t is computed on the host per PS step counter.  `scale` folds a 1/W gradient mean
 // (or 1.0 for the reference's sum) into the same pass.  HBM-bound: 5 streams of fp32;
 // 16-byte vector path (+ scalar tail) when every operand is 16-B aligned.
+// Momentum SGD (mu = 0: plain SGD, m left holding the scaled gradient): common.h momentum1,
+// 3 streams read and 2 written, the same two kernel shapes.
 #include "common.h"
 #include "api.h"
 
@@ -50,6 +52,30 @@ adam_scalar_kernel(float* __restrict__ w, const float* __restrict__ g, float* __
   }
 }
 
+// Momentum SGD, same shape as adam_vec_kernel: 3 streams read, 2 written, no v.  momentum1 pins
+// the roundings, so this and the scalar kernel below give the same bits.
+__global__ void __launch_bounds__(256)
+momentum_vec_kernel(float4* __restrict__ w, const float4* __restrict__ g, float4* __restrict__ m,
+                    int64_t n, float lr, float mu, float scale) {
+  const int64_t n4 = n >> 2;
+  const int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  for (int64_t i = gid; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    float4 W = w[i], G = g[i], M = m[i];
+    momentum1(W.x, G.x, M.x, lr, mu, scale);
+    momentum1(W.y, G.y, M.y, lr, mu, scale);
+    momentum1(W.z, G.z, M.z, lr, mu, scale);
+    momentum1(W.w, G.w, M.w, lr, mu, scale);
+    w[i] = W; m[i] = M;
+  }
+  if (gid < (n & 3)) {
+    const int64_t e = 4 * n4 + gid;
+    float* wf = reinterpret_cast<float*>(w);
+    float* mf = reinterpret_cast<float*>(m);
+    float W = wf[e], M = mf[e];
+    momentum1(W, reinterpret_cast<const float*>(g)[e], M, lr, mu, scale);
+    wf[e] = W; mf[e] = M;
+  }
+}
 __global__ void __launch_bounds__(256)
 momentum_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
                 int64_t n, float lr, float mu, float scale) {
@@ -92,10 +118,16 @@ void launch_adam_c(float* w, const float* g, float* m, float* v, int64_t n, floa
 }
 
 void launch_momentum(float* w, const float* g, float* m, int64_t n, float lr, float mu,
-                     float scale, hipStream_t st) {
+                     float scale, hipStream_t st, int max_grid) {
   if (n <= 0) return;
-  DDL_LAUNCH(momentum_kernel, dim3(grid_for(n)), dim3(256), 0, st, w, g, m, n, lr, mu,
-                     scale);
+  const uintptr_t al = (uintptr_t)w | (uintptr_t)g | (uintptr_t)m;
+  if ((al & 15) == 0) {
+    DDL_LAUNCH(momentum_vec_kernel, dim3(grid_for((n + 3) / 4, max_grid)), dim3(256), 0, st,
+               (float4*)w, (const float4*)g, (float4*)m, n, lr, mu, scale);
+  } else {
+    DDL_LAUNCH(momentum_kernel, dim3(grid_for(n, max_grid)), dim3(256), 0, st, w, g, m, n, lr,
+               mu, scale);
+  }
 }
 
 void launch_scale(float* p, int64_t n, float a, hipStream_t st) {

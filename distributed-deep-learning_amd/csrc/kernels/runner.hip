@@ -240,20 +240,29 @@ void SyncRunner::set_units(const std::vector<RunnerUnit>& units) {
       seg_pieces_[u.seg].push_back({r, u.ps, u.m, u.v});
     }
   coalesce(merged_);
-  tail_ok_ = true;
+  // tail_ok_: the shape fits for the momentum rule (w, g, m); tail_v_ok_: and every piece has a
+  // vector-shaped v, which the Adam rule needs.  Kept apart so that step() decides by opt_ at
+  // that time, whichever of set_optimizer / set_units came first.
+  tail_ok_ = tail_v_ok_ = true;
   auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   for (auto& sp : seg_pieces_) {
     coalesce(sp);
     tail_ok_ &= sp.size() <= (size_t)kTailPieces;
-    for (const auto& p : sp)
-      tail_ok_ &= p.v && (p.r.hi - p.r.lo) % 4 == 0 && a16(w_ + p.r.lo) && a16(g_ + p.r.lo) &&
-                  a16(p.m + p.r.state_off) && a16(p.v + p.r.state_off);
+    for (const auto& p : sp) {
+      tail_ok_ &= p.m && (p.r.hi - p.r.lo) % 4 == 0 && a16(w_ + p.r.lo) && a16(g_ + p.r.lo) &&
+                  a16(p.m + p.r.state_off);
+      tail_v_ok_ &= p.v && a16(p.v + p.r.state_off);
+    }
   }
 }
 
-// Segment `seg`'s Adam as the optimizer tail of the engine's next dual launch.
+// Segment `seg`'s update (Adam or momentum, by opt_) as the optimizer tail of the engine's next
+// dual launch.  Momentum: the step size is lr_, as in update(), and v stays null.
 void SyncRunner::set_tail(int seg, const float* lr_t, int f4_per_block) {
   UpdTail t;
+  const bool mom = opt_ == 1;
+  t.rule = mom ? kTailMomentum : kTailAdam;
+  t.mu = mu_;
   t.first = tail_first_;
   t.f4_per_block = f4_per_block > 0 ? f4_per_block : tail_f4_;
   t.c1 = 1.f - b1_;
@@ -266,9 +275,9 @@ void SyncRunner::set_tail(int seg, const float* lr_t, int f4_per_block) {
     q.w = w_ + p.r.lo;
     q.g = g_ + p.r.lo;
     q.m = p.m + p.r.state_off;
-    q.v = p.v + p.r.state_off;
+    q.v = mom ? nullptr : p.v + p.r.state_off;
     q.n = p.r.hi - p.r.lo;
-    q.lr_t = lr_t[p.ps];
+    q.lr_t = mom ? lr_ : lr_t[p.ps];
     q.blk0 = blk;
     blk += (int)((q.n / 4 + t.f4_per_block - 1) / t.f4_per_block);
   }
@@ -291,10 +300,17 @@ void SyncRunner::set_optimizer(int kind, float lr, float b1, float b2, float eps
 #endif
 void SyncRunner::update(float* w, const float* g, float* m, float* v, int64_t n, float lr_t,
                         hipStream_t st) {
+  const int max_grid = st == cs_ ? DDL_COMM_ADAM_GRID : 2048;
   if (opt_ == 0)
-    launch_adam_c(w, g, m, v, n, lr_t, 1.f - b1_, 1.f - b2_, eps_, grad_scale_, st,
-                  st == cs_ ? DDL_COMM_ADAM_GRID : 2048);
-  else launch_momentum(w, g, m, n, lr_, mu_, grad_scale_, st);
+    launch_adam_c(w, g, m, v, n, lr_t, 1.f - b1_, 1.f - b2_, eps_, grad_scale_, st, max_grid);
+  else launch_momentum(w, g, m, n, lr_, mu_, grad_scale_, st, max_grid);
+  upd_launches_ += n > 0;
+}
+
+// launch_scale of the coefficient path, counted like update()
+void SyncRunner::scale_grads(float* p, int64_t n, hipStream_t st) {
+  launch_scale(p, n, coef_, st);
+  upd_launches_ += n > 0;
 }
 
 void SyncRunner::issue(const RunnerUnit& u, const float* lr_t, hipStream_t st) {
@@ -303,7 +319,7 @@ void SyncRunner::issue(const RunnerUnit& u, const float* lr_t, hipStream_t st) {
     return;
   }
   if (coef_ != 1.f)
-    for (const auto& r : u.ranges) launch_scale(g_ + r.lo, r.hi - r.lo, coef_, st);
+    for (const auto& r : u.ranges) scale_grads(g_ + r.lo, r.hi - r.lo, st);
   const float lt = lr_t[u.ps];
   switch (u.kind) {
     case RunnerUnit::LOCAL:
@@ -344,7 +360,7 @@ void SyncRunner::issue_reduce_group(const std::vector<const RunnerUnit*>& us, co
                                     hipStream_t st) {
   for (const RunnerUnit* u : us)
     if (coef_ != 1.f)
-      for (const auto& r : u->ranges) launch_scale(g_ + r.lo, r.hi - r.lo, coef_, st);
+      for (const auto& r : u->ranges) scale_grads(g_ + r.lo, r.hi - r.lo, st);
   RCCL_CHECK(rccl().GroupStart());
   for (const RunnerUnit* u : us)
     for (const auto& r : u->ranges)
@@ -374,6 +390,7 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
                       const float* lr_t, hipStream_t st) {
   if (closed_) throw std::runtime_error("sync runner: step() after close()");
   TraceRange step_range("ddl.step");
+  upd_launches_ = eng_->update_launches = 0;  // (host counters: update_launches())
   eng_->seed_value = seed_value;  // dropout seed by kernel argument: no seed-upload kernel
   const uint32_t* seed = nullptr;
   // Cross-queue dependencies (event record -> stream wait) cost tens of microseconds of GPU
@@ -384,7 +401,9 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
     TraceRange r("ddl.fwd");
     eng_->forward(x, B, seed, true, st, /*defer_fc2=*/true);  // backward_segment(0) follows
   }
-  if (all_local_ && local_on_main_ && use_tail_ && tail_ok_ && opt_ == 0 && coef_ == 1.f) {
+  // (Adam needs every piece's v; momentum / SGD have none and form none)
+  if (all_local_ && local_on_main_ && use_tail_ && tail_ok_ && (opt_ == 1 || tail_v_ok_) &&
+      coef_ == 1.f) {
     // segment s-1's update rides in segment s's dual launch (flushed as a launch of its own
     // if the segment had no dual launch to take it); the last segment's follows the backward
     for (int s = 0; s < kSegments; ++s) {
@@ -408,7 +427,7 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
     eng_->final_upd = UpdTail();
     TraceRange r("ddl.update.last_segment");
     for (const auto& p : seg_pieces_[kSegments - 1])
-      update(w_ + p.r.lo, g_ + p.r.lo, p.m + p.r.state_off, p.v + p.r.state_off,
+      update(w_ + p.r.lo, g_ + p.r.lo, p.m + p.r.state_off, p.v ? p.v + p.r.state_off : nullptr,
              p.r.hi - p.r.lo, lr_t[p.ps], st);
     return;
   }
@@ -419,7 +438,7 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
     }
     TraceRange r("ddl.update");
     if (coef_ != 1.f)
-      for (const auto& p : merged_) launch_scale(g_ + p.r.lo, p.r.hi - p.r.lo, coef_, st);
+      for (const auto& p : merged_) scale_grads(g_ + p.r.lo, p.r.hi - p.r.lo, st);
     for (const auto& p : merged_)
       update(w_ + p.r.lo, g_ + p.r.lo, p.m + p.r.state_off, p.v ? p.v + p.r.state_off : nullptr,
              p.r.hi - p.r.lo, lr_t[p.ps], st);

@@ -7,7 +7,8 @@
 // no later backward launch reads that segment's parameters, so the update of segment s can
 // run as extra blocks of segment s+1's dual dgrad+wgrad launch: memory-bound blocks beside
 // MFMA-bound ones, hidden instead of serialised.  Only the last segment's (conv1 + conv2,
-// 52 k parameters) update remains a launch of its own.
+// 52 k parameters) update remains a launch of its own.  Momentum and plain SGD take the same
+// slots (UpdTail::rule): w, g, m only, so 5 streams instead of 7 and no v anywhere.
 //
 // The asynchronous worker step (async_runner.hip) uses the same slot for its gradient PUSH
 // (kind 1): segment s's shards are stored into their PS hosts' inboxes and posted on the
@@ -37,9 +38,9 @@ struct UpdPiece {
   float* w = nullptr;      // 16-B aligned, n % 4 == 0 (checked by the host); push: the inbox slot
   const float* g = nullptr;  // push: the gradient shard
   float* m = nullptr;
-  float* v = nullptr;
+  float* v = nullptr;      // null under the momentum rule
   int64_t n = 0;           // elements
-  float lr_t = 0.f;        // TF1 Adam step size of the owning PS
+  float lr_t = 0.f;        // TF1 Adam step size of the owning PS (momentum: the learning rate)
   int blk0 = 0;            // first tail block of this piece
   // push (kind 1): slice j = block blk0 + j covers float4 [j * slice4, (j + 1) * slice4); its
   // board word posted[j] (host memory).  Ready flag
@@ -49,16 +50,22 @@ struct UpdPiece {
   int slice4 = 0, nslice = 0;
 };
 
+constexpr int kTailAdam = 0, kTailMomentum = 1;  // UpdTail::rule
+
 struct UpdTail {
   int nblocks = 0;         // tail blocks (multiple of 8: keeps the GEMM blocks' XCD mapping)
   int npieces = 0;
-  int kind = 0;            // 0: Adam update, 1: asynchronous gradient push (round `epoch`),
+  int kind = 0;            // 0: update (`rule`), 1: asynchronous gradient push (round `epoch`),
                            // 2: ready flag (p[0].arrive[0] = epoch)
   uint32_t epoch = 0;
   int first = 1;           // 1: tail blocks precede the GEMM blocks in the grid, 0: follow them
   int f4_per_block = kTailF4PerBlock;  // float4 per tail block (multiple of kTailF4PerBlock)
   UpdPiece p[kTailPieces];
   float c1 = 0.f, c2 = 0.f, eps = 0.f, scale = 1.f;  // 1 - beta1, 1 - beta2, epsilon, grad scale
+  // kind 0's update rule: kTailAdam, or kTailMomentum (common.h momentum1; mu = 0: plain SGD):
+  // the pieces' v is null and never formed, lr_t is the plain learning rate
+  int rule = kTailAdam;
+  float mu = 0.f;
 };
 
 }  // namespace ddl

@@ -2,7 +2,13 @@
 """Step time of the W = 1 native runner with the optimizer tail (csrc/kernels/tail.h) off and
 in several placements / block sizes, interleaved rounds in one process.
 
-usage: python scripts/tail_probe.py [--steps 300] [--rounds 3]
+--optimizer takes one or more of adam / momentum / sgd: each gets a trainer of its own, and
+every round visits every (optimizer, variant) pair in turn, so optimizers are compared under
+the same conditions as tail variants.  --variants default keeps the comparison to the tail
+off and the runner's default placement.
+
+usage: python scripts/tail_probe.py [--steps 300] [--rounds 3] [--optimizer momentum]
+       python scripts/tail_probe.py --optimizer adam momentum sgd --variants default
 """
 import argparse
 import os
@@ -17,6 +23,11 @@ def main():
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--shard", default="flat")
+    ap.add_argument("--optimizer", nargs="+", default=["adam"],
+                    choices=["adam", "momentum", "sgd"])
+    ap.add_argument("--variants", default="sweep", choices=["sweep", "default"],
+                    help="sweep: off + both placements x 4 block sizes; default: off + the "
+                         "runner's default tail")
     a = ap.parse_args()
     import torch
     from ddl_amd.config import TrainConfig
@@ -25,33 +36,45 @@ def main():
     from ddl_amd.utils.data import synthetic_mnist
 
     env = DistEnv(0, 1, 0, torch.device("cuda", 0))
-    cfg = TrainConfig(mode="sync", shard=a.shard, steps=10 ** 6, batch_size=100, eval_every=0,
-                      engine="hip", quiet=True, data_sharding="stride")
-    tr = Trainer(cfg, env, dataset=synthetic_mnist())
-    run = tr.exchange.runner
-    variants = [("off", None)] + [(f"{'first' if f else 'last'}-f4x{n}", (f, n))
-                                  for f in (1, 0) for n in (512, 1024, 2048, 4096)]
-    res = {k: [] for k, _ in variants}
+    data = synthetic_mnist()
+    trainers = {}
+    for opt in dict.fromkeys(a.optimizer):
+        cfg = TrainConfig(mode="sync", shard=a.shard, steps=10 ** 6, batch_size=100, eval_every=0,
+                          engine="hip", quiet=True, data_sharding="stride", optimizer=opt)
+        trainers[opt] = Trainer(cfg, env, dataset=data)
+    if a.variants == "default":
+        variants = [("off", None), ("tail", ())]
+    else:
+        variants = [("off", None)] + [(f"{'first' if f else 'last'}-f4x{n}", (f, n))
+                                      for f in (1, 0) for n in (512, 1024, 2048, 4096)]
+    res = {(o, k): [] for o in trainers for k, _ in variants}
+    launches = {}
     step = 0
     for _ in range(a.rounds):
         for name, v in variants:
-            if v is None:
-                run.set_use_tail(False)
-            else:
-                run.set_use_tail(True)
-                run.set_tail_cfg(*v)
-            for _ in range(20):
-                tr.train_step(step)
-                step += 1
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(a.steps):
-                tr.train_step(step)
-                step += 1
-            torch.cuda.synchronize()
-            res[name].append(1e6 * (time.perf_counter() - t0) / a.steps)
-    for name, ts in res.items():
-        print(f"{name:16s} us/step min {min(ts):7.1f}  all {' '.join(f'{t:.1f}' for t in ts)}")
+            for opt, tr in trainers.items():
+                run = tr.exchange.runner
+                if v is None:
+                    run.set_use_tail(False)
+                else:
+                    run.set_use_tail(True)
+                    if v:
+                        run.set_tail_cfg(*v)
+                for _ in range(20):
+                    tr.train_step(step)
+                    step += 1
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    tr.train_step(step)
+                    step += 1
+                torch.cuda.synchronize()
+                res[opt, name].append(1e6 * (time.perf_counter() - t0) / a.steps)
+                launches[opt, name] = run.update_launches()
+    for (opt, name), ts in res.items():
+        print(f"{opt:9s}{name:16s} us/step min {min(ts):7.1f}  spread {max(ts) - min(ts):5.1f}  "
+              f"all {' '.join(f'{t:.1f}' for t in ts)}  update launches/step "
+              f"{launches[opt, name]}")
 
 
 if __name__ == "__main__":
