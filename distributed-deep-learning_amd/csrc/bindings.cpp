@@ -25,27 +25,44 @@ void check_f32_cuda(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
 
+// One update of a flat span under rule `kind` of update.h (copy: m and v may be None; momentum:
+// v may be).  The step size rides beside it: Adam's lr_t, or the learning rate.
+struct FlatUpdate {
+  ddl::UpdRule rule;
+  ddl::UpdSpan span;
+  const float* g;
+  int64_t n;
+  FlatUpdate(int64_t kind, at::Tensor w, at::Tensor gt, c10::optional<at::Tensor> m,
+             c10::optional<at::Tensor> v, double b1, double b2, double eps, double mu,
+             double scale)
+      : rule((int)kind, (float)b1, (float)b2, (float)eps, (float)mu, (float)scale), n(w.numel()) {
+    TORCH_CHECK(kind >= 0 && kind <= 2, "update: rule kind");
+    TORCH_CHECK((m || kind == ddl::kUpdCopy) && (v || kind != ddl::kUpdAdam),
+                "update: optimizer state missing");
+    auto ptr = [&](const at::Tensor& t, const char* name) {
+      check_f32_cuda(t, name);
+      TORCH_CHECK(t.numel() == n, "update: size mismatch");
+      return t.data_ptr<float>();
+    };
+    span.w = ptr(w, "w");
+    g = ptr(gt, "g");
+    if (m) span.m = ptr(*m, "m");
+    if (v) span.v = ptr(*v, "v");
+  }
+};
+
+void update_flat(int64_t kind, at::Tensor w, at::Tensor g, c10::optional<at::Tensor> m,
+                 c10::optional<at::Tensor> v, double step, double b1, double b2, double eps,
+                 double mu, double scale) {
+  const FlatUpdate u(kind, w, g, m, v, b1, b2, eps, mu, scale);
+  ddl::launch_update(u.rule, (float)step, u.span, u.g, u.n, cur_stream());
+}
 void adam_flat(at::Tensor w, at::Tensor g, at::Tensor m, at::Tensor v, double lr_t, double b1,
                double b2, double eps, double scale) {
-  check_f32_cuda(w, "w");
-  check_f32_cuda(g, "g");
-  check_f32_cuda(m, "m");
-  check_f32_cuda(v, "v");
-  const int64_t n = w.numel();
-  TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n, "adam_flat: size mismatch");
-  ddl::launch_adam(w.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
-                   v.data_ptr<float>(), n, (float)lr_t, (float)b1, (float)b2, (float)eps,
-                   (float)scale, cur_stream());
+  update_flat(ddl::kUpdAdam, w, g, m, v, lr_t, b1, b2, eps, 0.0, scale);
 }
-
 void momentum_flat(at::Tensor w, at::Tensor g, at::Tensor m, double lr, double mu, double scale) {
-  check_f32_cuda(w, "w");
-  check_f32_cuda(g, "g");
-  check_f32_cuda(m, "m");
-  const int64_t n = w.numel();
-  TORCH_CHECK(g.numel() == n && m.numel() == n, "momentum_flat: size mismatch");
-  ddl::launch_momentum(w.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), n,
-                       (float)lr, (float)mu, (float)scale, cur_stream());
+  update_flat(ddl::kUpdMomentum, w, g, m, c10::nullopt, lr, 0.0, 0.0, 0.0, mu, scale);
 }
 
 // Python-facing wrapper of ddl::Engine: owns the workspace tensor.
@@ -109,6 +126,22 @@ class PyEngine {
     e_.concurrent = on;
   }
   void set_dual(bool on) { e_.dual = on; }
+  // the same update as a one-piece optimizer tail that no launch takes: Engine::flush_tail's
+  // stand-alone launch (tests)
+  void flush_update_tail(int64_t kind, at::Tensor w, at::Tensor g, c10::optional<at::Tensor> m,
+                         c10::optional<at::Tensor> v, double step, double b1, double b2,
+                         double eps, double mu, double scale) {
+    const FlatUpdate u(kind, w, g, m, v, b1, b2, eps, mu, scale);
+    e_.flush_tail(cur_stream());
+    ddl::UpdPiece q;
+    q.w = u.span.w; q.g = u.g; q.m = u.span.m; q.v = u.span.v;
+    q.n = u.n;
+    q.step = (float)step;
+    e_.tail.rule = u.rule;
+    e_.tail.add_piece(q);
+    e_.tail.finish();
+    e_.flush_tail(cur_stream());
+  }
   void set_wide_thr(int64_t t) {
     e_.wide_thr = (int)std::max<int64_t>(1, t);
     for (int i = 0; i < ddl::OP_COUNT; ++i) e_.wide[i] = e_.wide_thr;
@@ -340,22 +373,17 @@ class PyAsyncPeer {
     py::gil_scoped_release nogil;
     return p_->wait_done((uint32_t)epoch, timeout_s);
   }
-  // opt: 0 Adam (lr_t, b1, b2, eps), 1 momentum (lr, mu), 2 self-test
+  // opt: update.h's rule kind (0 Adam: the step size is lr_t; 1 momentum: lr; 2 self-test).
+  // (both step sizes stay in the Python-facing signature: parallel/async_xgmi.py is unchanged)
   void apply(int64_t ps, int64_t worker, int64_t epoch, int64_t opt, at::Tensor ps_params,
              c10::optional<at::Tensor> m, c10::optional<at::Tensor> v, double lr_t, double b1,
              double b2, double eps, double lr, double mu, double scale) {
     check_f32_cuda(ps_params, "ps_params");
     ddl::XgmiUpdate u;
-    u.opt = (int)opt;
+    u.rule = ddl::UpdRule((int)opt, (float)b1, (float)b2, (float)eps, (float)mu, (float)scale);
+    u.step = (float)(opt == ddl::kUpdMomentum ? lr : lr_t);
     if (m) { check_f32_cuda(*m, "m"); u.m = m->data_ptr<float>(); }
     if (v) { check_f32_cuda(*v, "v"); u.v = v->data_ptr<float>(); }
-    u.lr_t = (float)lr_t;
-    u.c1 = 1.f - (float)b1;
-    u.c2 = 1.f - (float)b2;
-    u.eps = (float)eps;
-    u.lr = (float)lr;
-    u.mu = (float)mu;
-    u.scale = (float)scale;
     p_->apply((int)ps, (int)worker, (uint32_t)epoch, u, ps_params.data_ptr<float>(), cur_stream());
   }
   void close() {
@@ -709,6 +737,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("w"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("lr_t"), py::arg("b1"),
         py::arg("b2"), py::arg("eps"), py::arg("scale") = 1.0);
   m.def("momentum_flat", &momentum_flat, "Fused momentum SGD on a flat shard");
+  m.def("update_flat", &update_flat, "One update of a flat shard under rule `kind` (update.h)",
+        py::arg("kind"), py::arg("w"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("step"),
+        py::arg("b1") = 0.0, py::arg("b2") = 0.0, py::arg("eps") = 0.0, py::arg("mu") = 0.0,
+        py::arg("scale") = 1.0);
+  m.def("adam_step_size", [](double lr, double b1, double b2, int64_t t) {
+          return (double)ddl::adam_step_size(lr, b1, b2, t);
+        }, "TF1 Adam's lr_t at step t as the native runtime forms it (float32, returned widened)");
   // per-block timestamps of the split-K dual launches (kernels/stamps.h; a build with
   // DDL_STAMPS=1 records them, the default build records nothing)
   m.def("stamps_enabled", []() { return (bool)DDL_STAMPS; });
@@ -776,6 +811,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("get_eval_cfg", &PyEngine::get_eval_cfg)
       .def("set_concurrent", &PyEngine::set_concurrent)
       .def("set_dual", &PyEngine::set_dual)
+      .def("flush_update_tail", &PyEngine::flush_update_tail)
       .def("set_conv1_direct", [](PyEngine& e, bool on) { e.raw()->conv1_direct = on; })
       .def("conv1_direct", [](PyEngine& e) { return e.raw()->conv1_direct; })
       .def("set_conv1_wgrad_direct", [](PyEngine& e, bool on) { e.raw()->conv1_wgrad_direct = on; })

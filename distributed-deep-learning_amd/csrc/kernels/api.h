@@ -26,14 +26,11 @@ namespace ddl {
 class ShmMailbox;
 
 // ---- optimizer (optim.hip) -------------------------------------------------------------------
-void launch_adam(float* w, const float* g, float* m, float* v, int64_t n, float lr_t, float b1,
-                 float b2, float eps, float scale, hipStream_t st);
-// same with c1 = 1 - beta1, c2 = 1 - beta2 precomputed (bit-identical to launch_adam)
-void launch_adam_c(float* w, const float* g, float* m, float* v, int64_t n, float lr_t, float c1,
-                   float c2, float eps, float scale, hipStream_t st, int max_grid = 2048);
-// 16-B vector kernel when w, g and m are 16-B aligned, else the scalar one (bit-identical)
-void launch_momentum(float* w, const float* g, float* m, int64_t n, float lr, float mu,
-                     float scale, hipStream_t st, int max_grid = 2048);
+// One update of span s from gradient g under rule r (update.h) with step size `step`: the 16-B
+// vector kernel when every stream the rule has is 16-B aligned, else the scalar one (the same
+// bits).  Every stand-alone optimizer launch of the runtime goes through here.
+void launch_update(const UpdRule& r, float step, const UpdSpan& s, const float* g, int64_t n,
+                   hipStream_t st, int max_grid = 2048);
 void launch_scale(float* p, int64_t n, float a, hipStream_t st);
 
 // ---- conv1 forward as a direct LDS-staged kernel (conv1.hip) --------------------------------
@@ -260,14 +257,15 @@ struct XgmiTable {               // every rank's IPC-mapped buffers, indexed by 
   uint32_t* flags[kXgmiMaxPeers];
 };
 struct XgmiLaunch {              // one bucket's kernel arguments
-  int world, rank, bucket, nbuckets, final_wait, opt;
+  int world, rank, bucket, nbuckets, final_wait;
   uint32_t epoch;
   int64_t lo, c, inbox_off, slice;
   int nslices[kXgmiMaxBuckets];
   const float* grads;
   float* m;
   float* v;
-  float lr_t, c1, c2, eps, lr, mu, scale, coef;
+  UpdRule rule;                  // the owner-side update (update.h) and its step size
+  float step, coef;
   int* err;
   long long timeout_ticks;
   int check;                     // DDL_XGMI_CHECK: per-(bucket, source, slice) inbox checksums
@@ -296,11 +294,11 @@ struct XgmiBucketSpec {
   int owner = -1;
 };
 struct XgmiUpdate {              // owner-side update of one bucket chunk
-  int opt = 0;                   // 0 Adam (TF1), 1 momentum, 2 self-test (w := summed g)
+  UpdRule rule;                  // update.h (kUpdCopy: the self-test, w := summed g)
+  float step = 0.f;              // Adam: lr_t of the owning PS; momentum: the learning rate
   float* m = nullptr;            // optimizer state of this rank's chunk of the bucket
   float* v = nullptr;
-  float lr_t = 0.f, c1 = 0.1f, c2 = 0.001f, eps = 1e-8f, lr = 0.f, mu = 0.9f;
-  float scale = 1.f, coef = 1.f;
+  float coef = 1.f;
 };
 
 // The xGMI self-test's stale-L2 probe (xgmi.hip): every XCD reads every line of `a` (want null:
@@ -492,8 +490,8 @@ class AsyncService {
   AsyncPeer* peer_;
   int world_, device_;
   std::vector<AsyncPsState> ps_;
-  int opt_;
-  float lr_, b1_, b2_, eps_, mu_, scale_;
+  UpdRule rule_;
+  float lr_, b1_, b2_;           // widened to double for adam_step_size (update.h)
   bool keep_prov_;
   std::vector<uint32_t> epoch_;
   std::vector<std::array<int64_t, 4>> prov_;
@@ -546,7 +544,8 @@ class AsyncRunner {
   UpdTail inline_tail(int seg, int f4_per_block);
   bool inline_ = false, keep_prov_ = false;
   std::vector<AsyncPsState> ips_;  // by PS id
-  float lr_ = 0.f, b1_ = 0.f, b2_ = 0.f, eps_ = 0.f, scale_ = 1.f;
+  UpdRule rule_;                   // Adam (the in-line applies have no other rule)
+  float lr_ = 0.f, b1_ = 0.f, b2_ = 0.f;  // widened to double for adam_step_size (update.h)
   std::vector<float> lr_t_;        // this round's TF1 Adam step size per PS
   std::vector<std::array<int64_t, 4>> prov_;
   hipStream_t last_st_ = nullptr;
@@ -601,9 +600,9 @@ class RcclAsync {
   std::vector<std::pair<int64_t, int64_t>> ranges_;
   std::vector<int> hosts_;
   std::vector<AsyncPsState> ps_;
-  int opt_;
-  float lr_, b1_, b2_, eps_, mu_;
-  double lrd_, b1d_, b2d_;
+  UpdRule rule_;                 // (scale 1: the workers push unscaled gradients)
+  float lr_;                     // momentum's step size
+  double lrd_, b1d_, b2d_;       // adam_step_size in true doubles, as ops/adam.py
   bool self_;
   void* comm_ = nullptr;
   hipStream_t cs_ = nullptr;
@@ -642,7 +641,7 @@ class SyncRunner {
   bool has_comm() const { return comm_ != nullptr; }
   void set_units(const std::vector<RunnerUnit>& units);
   void set_optimizer(int kind, float lr, float b1, float b2, float eps, float mu);
-  void set_scale(float grad_scale, float coef) { grad_scale_ = grad_scale; coef_ = coef; }
+  void set_scale(float grad_scale, float coef) { rule_.scale = grad_scale; coef_ = coef; }
   // one synchronous training step on stream `st`; lr_t indexed by RunnerUnit::ps
   void step(const float* x, const int64_t* labels, int B, uint32_t seed, const float* lr_t,
             hipStream_t st);
@@ -677,8 +676,7 @@ class SyncRunner {
   // group of broadcasts (instead of two groups per unit)
   void issue_reduce_group(const std::vector<const RunnerUnit*>& us, const float* lr_t,
                           hipStream_t st);
-  void update(float* w, const float* g, float* m, float* v, int64_t n, float lr_t,
-              hipStream_t st);
+  void update(const UpdSpan& s, const float* g, int64_t n, float lr_t, hipStream_t st);
   void scale_grads(float* p, int64_t n, hipStream_t st);  // g *= coef_
   int upd_launches_ = 0;
   void issue_xgmi(const RunnerUnit& u, const float* lr_t, bool final_wait, hipStream_t st,
@@ -715,9 +713,15 @@ class SyncRunner {
   double gate_timeout_s_ = 20.0;  // DDL_XGMI_TIMEOUT_S
   uint32_t ready_epoch_ = 0;      // one per step
   std::vector<RunnerUnit> units_;
-  int opt_ = 0;
-  float lr_ = 1e-4f, b1_ = 0.9f, b2_ = 0.999f, eps_ = 1e-8f, mu_ = 0.9f;
-  float grad_scale_ = 1.f, coef_ = 1.f;
+  UpdRule rule_{kUpdAdam, 0.9f, 0.999f, 1e-8f, 0.9f, 1.f};  // (scale: set_scale's grad_scale)
+  float lr_ = 1e-4f;       // momentum's step size (Adam's lr_t comes with every step())
+  float coef_ = 1.f;
+  // a range's parameter / optimizer-state span (state at state_off of the owning PS's m / v)
+  UpdSpan span_of(const RunnerRange& r, float* m, float* v) const {
+    return UpdSpan{w_ + r.lo, m + r.state_off, v ? v + r.state_off : nullptr};
+  }
+  // the step size under the current rule, given the owning PS's Adam lr_t
+  float step_of(float lr_t) const { return rule_.kind == kUpdMomentum ? lr_ : lr_t; }
   bool local_on_main_ = true;
   bool last_on_main_ = true;
   struct Piece {

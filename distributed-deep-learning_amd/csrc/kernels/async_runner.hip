@@ -106,11 +106,10 @@ void AsyncRunner::set_inline(const std::vector<AsyncPsState>& ps, float lr, floa
     by[s.ps] = s;
   }
   ips_ = by;
+  rule_ = UpdRule(kUpdAdam, b1, b2, eps, 0.f, scale);
   lr_ = lr;
   b1_ = b1;
   b2_ = b2;
-  eps_ = eps;
-  scale_ = scale;
   keep_prov_ = provenance;
   prov_.clear();
   lr_t_.assign(P, 0.f);
@@ -142,26 +141,21 @@ UpdTail AsyncRunner::inline_tail(int seg, int f4_per_block) {
   if ((int)seg_ps_[seg].size() > kTailPieces) return t;
   t.first = 0;
   t.f4_per_block = f4_per_block;
-  t.c1 = 1.f - b1_;
-  t.c2 = 1.f - b2_;
-  t.eps = eps_;
-  t.scale = scale_;
-  int blk = 0;
+  t.rule = rule_;
   for (int p : seg_ps_[seg]) {
     int64_t lo = 0, n = 0;
     int host = -1;
     peer_->shard(p, lo, n, host);
-    UpdPiece& q = t.p[t.npieces++];
+    UpdPiece q;
     q.w = peer_->params() + lo;
     q.g = peer_->grads() + lo;
     q.m = ips_[p].m;
     q.v = ips_[p].v;
     q.n = n;
-    q.lr_t = lr_t_[p];
-    q.blk0 = blk;
-    blk += (int)((n / 4 + f4_per_block - 1) / f4_per_block);
+    q.step = lr_t_[p];
+    t.add_piece(q);
   }
-  t.nblocks = (blk + 7) & ~7;
+  t.finish();
   return t;
 }
 
@@ -170,8 +164,7 @@ void AsyncRunner::step_inline(const float* x, const int64_t* labels, int B, hipS
   // one Adam step of each PS's own counter per push (TF1: lr_t = lr sqrt(1 - b2^t) / (1 - b1^t))
   for (size_t p = 0; p < ips_.size(); ++p) {
     const int64_t t = ++ips_[p].t;
-    lr_t_[p] = (float)((double)lr_ * std::sqrt(1.0 - std::pow((double)b2_, (double)t)) /
-                       (1.0 - std::pow((double)b1_, (double)t)));
+    lr_t_[p] = adam_step_size(lr_, b1_, b2_, t);
     if (keep_prov_) prov_.push_back({(int64_t)rank_, (int64_t)p, (int64_t)epoch_, t});
   }
   {
@@ -183,8 +176,8 @@ void AsyncRunner::step_inline(const float* x, const int64_t* labels, int B, hipS
       int64_t lo = 0, n = 0;
       int host = -1;
       peer_->shard(p, lo, n, host);
-      launch_adam_c(peer_->params() + lo, peer_->grads() + lo, ips_[p].m, ips_[p].v, n,
-                    lr_t_[p], 1.f - b1_, 1.f - b2_, eps_, scale_, st);
+      launch_update(rule_, lr_t_[p], UpdSpan{peer_->params() + lo, ips_[p].m, ips_[p].v},
+                    peer_->grads() + lo, n, st);
     }
   };
   for (int s = 0; s < kSegments; ++s) {

@@ -84,11 +84,19 @@ DDL_DEV f32x4 mfma16x16x4(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-// TF1 ApplyAdam update of one element (TF's update form, documented in optim.hip).
-DDL_DEV void adam1(float& w, float g, float& m, float& v, float lr_t, float c1, float c2,
-                   float eps) {
-  m += (g - m) * c1;
-  v += (g * g - v) * c2;
+// TF1 ApplyAdam update of one element from the raw gradient g and its scale (TF's update form,
+// documented in optim.hip).  The roundings of m and v are pinned, as momentum1's below, so no
+// site's result depends on the compiler's contraction choices: left to them, the scalar flat
+// kernel formed m with a separate product and sum where every other site fused them (the two
+// flat kernels differed in m's last bit), and whether g * scale fused into g - m was each
+// site's luck.  The pinned form is the one those other sites compiled to: the difference is one
+// fma on the unrounded product, v uses the rounded product.  Every multiply below feeds an
+// explicit fma or the division, so nothing is left to contract, here or across the call.
+DDL_DEV void adam1(float& w, float g, float scale, float& m, float& v, float lr_t, float c1,
+                   float c2, float eps) {
+  const float gs = g * scale;
+  m = __fmaf_rn(__fmaf_rn(g, scale, -m), c1, m);
+  v = __fmaf_rn(__fmaf_rn(gs, gs, -v), c2, v);
   w -= lr_t * m / (sqrtf(v) + eps);
 }
 

@@ -30,12 +30,10 @@ constexpr int kC1wLdsBand = 18 * kC1wPitch + 2;  // (+2: keeps the partials 16-B
 // optional optimizer on conv1's weight / bias as the final reduce writes them (the W = 1 tail
 // path: the last segment's update needs no launch of its own); on = 0: gradients only
 struct C1Adam {
-  float *w_w = nullptr, *w_m = nullptr, *w_v = nullptr;  // weight [800] spans
-  float *b_w = nullptr, *b_m = nullptr, *b_v = nullptr;  // bias [32] spans
-  float lr_t = 0.f, c1 = 0.f, c2 = 0.f, eps = 0.f, scale = 1.f;
+  UpdSpan wt, bias;  // weight [800] and bias [32] spans (update.h; v null under momentum)
+  UpdRule rule;
+  float step = 0.f;
   int on = 0;
-  int rule = kTailAdam;  // tail.h: kTailMomentum applies momentum1 (w_v / b_v null, untouched)
-  float mu = 0.f;
 };
 constexpr int kC1wElems = 26 * 32; // dW_aug[26][32] (row 25: db)
 
@@ -96,27 +94,31 @@ DDL_DEV void c1w_accum(brsrc_t part, int src, int n, float (&s)[kC1wEPT]) {
   }
 }
 
+// the final level's sums `s` into gw / gb, each element updated under rule KIND as it is stored
+template <int KIND>
+DDL_DEV void c1w_store_update(const float (&s)[kC1wEPT], float* gw, float* gb, const C1Adam& ad) {
+#pragma unroll
+  for (int j = 0; j < kC1wEPT; ++j) {
+    const int e = (int)threadIdx.x + 256 * j;
+    if (e >= kC1wElems) continue;
+    const bool wrow = e < 25 * 32;
+    const int i = wrow ? e : e - 25 * 32;
+    (wrow ? gw : gb)[i] = s[j];
+    upd1_at<KIND>(ad.rule, ad.step, wrow ? ad.wt.w : ad.bias.w, s[j], wrow ? ad.wt.m : ad.bias.m,
+                  wrow ? ad.wt.v : ad.bias.v, i);
+  }
+}
+
 template <int U>
 DDL_DEV void c1w_sum(brsrc_t part, int src, int n, brsrc_t out, int dst, float* gw, float* gb,
                      const C1Adam* ad = nullptr) {
   constexpr int EPT = kC1wEPT;
   float s[EPT];
   c1w_accum<U>(part, src, n, s);
-  // the momentum rule in a loop of its own, chosen once: the Adam loop below stays as it was
-  if (gw && ad && ad->on && ad->rule == kTailMomentum) {
-#pragma unroll
-    for (int j = 0; j < EPT; ++j) {
-      const int e = (int)threadIdx.x + 256 * j;
-      if (e >= kC1wElems) continue;
-      const bool wrow = e < 25 * 32;
-      const int i = wrow ? e : e - 25 * 32;
-      (wrow ? gw : gb)[i] = s[j];
-      float* pw = wrow ? ad->w_w : ad->b_w;
-      float* pm = wrow ? ad->w_m : ad->b_m;
-      float W = pw[i], M = pm[i];
-      momentum1(W, s[j], M, ad->lr_t, ad->mu, ad->scale);
-      pw[i] = W; pm[i] = M;
-    }
+  // one update loop, templated on the rule's kind and chosen once (block-uniform)
+  if (gw && ad && ad->on) {
+    if (ad->rule.kind == kUpdMomentum) c1w_store_update<kUpdMomentum>(s, gw, gb, *ad);
+    else c1w_store_update<kUpdAdam>(s, gw, gb, *ad);
     return;
   }
 #pragma unroll
@@ -127,14 +129,6 @@ DDL_DEV void c1w_sum(brsrc_t part, int src, int n, brsrc_t out, int dst, float* 
       const bool wrow = e < 25 * 32;
       const int i = wrow ? e : e - 25 * 32;
       (wrow ? gw : gb)[i] = s[j];
-      if (ad && ad->on) {
-        float* pw = wrow ? ad->w_w : ad->b_w;
-        float* pm = wrow ? ad->w_m : ad->b_m;
-        float* pv = wrow ? ad->w_v : ad->b_v;
-        float W = pw[i], M = pm[i], V = pv[i];
-        adam1(W, s[j] * ad->scale, M, V, ad->lr_t, ad->c1, ad->c2, ad->eps);
-        pw[i] = W; pm[i] = M; pv[i] = V;
-      }
     } else {
       bstore1_sc1(out, (dst * kC1wElems + e) * 4, s[j]);
     }

@@ -240,10 +240,7 @@ void Engine::flush_tail(hipStream_t st) {
   }
   for (int i = 0; i < tail.npieces; ++i) {
     const UpdPiece& p = tail.p[i];
-    if (tail.rule == kTailMomentum)
-      launch_momentum(p.w, p.g, p.m, p.n, p.lr_t, tail.mu, tail.scale, st);
-    else
-      launch_adam_c(p.w, p.g, p.m, p.v, p.n, p.lr_t, tail.c1, tail.c2, tail.eps, tail.scale, st);
+    launch_update(tail.rule, p.step, p.span(0), p.g, p.n, st);
     update_launches += p.n > 0;
   }
   tail = UpdTail();

@@ -323,41 +323,35 @@ void run_dual_inst(Engine& e, const float* x, int B, const uint32_t* seed, hipSt
 // Split the last segment's update `in` into conv1's weight / bias spans (applied by the
 // epilogue of conv1's weight-gradient reduce: `pa`) and the remaining ranges (`rest`, tail
 // blocks of that launch).  false: the layout does not allow it (the caller keeps `in`).
-// (a momentum tail's v is null: no arithmetic on it)
-inline float* span_at(float* p, int64_t off) { return p ? p + off : nullptr; }
-
+// (UpdSpan::at: a momentum tail's v is null, no arithmetic on it)
 template <class PN>
 inline bool final_split(const Engine& e, const UpdTail& in, const PN& pn, WgradAdam<PN>& pa,
                         UpdTail& rest) {
-  struct Span { const float* w; int64_t n; float *pw = nullptr, *pm = nullptr, *pv = nullptr;
-                float lr_t = 0.f; };
-  Span sp[2] = {{e.P[0], (int64_t)PN::KW * pn.N}, {e.P[1], (int64_t)pn.N}};
+  struct Want { const float* w; int64_t n; UpdSpan s; float step = 0.f; };
+  Want sp[2] = {{e.P[0], (int64_t)PN::KW * pn.N}, {e.P[1], (int64_t)pn.N}};
   rest = in;
-  rest.npieces = 0;
-  int blk = 0;
+  rest.npieces = rest.nblocks = 0;
   auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   auto keep = [&](const UpdPiece& p, int64_t lo, int64_t hi) {
     if (hi <= lo) return true;
-    if ((hi - lo) % 4 || rest.npieces >= kTailPieces) return false;
+    if ((hi - lo) % 4) return false;
     UpdPiece q = p;
-    q.w = p.w + lo; q.g = p.g + lo; q.m = p.m + lo; q.v = span_at(p.v, lo);
+    const UpdSpan s = p.span(lo);
+    q.w = s.w; q.g = p.g + lo; q.m = s.m; q.v = s.v;
     if (!a16(q.w) || !a16(q.g) || !a16(q.m) || !a16(q.v)) return false;
     q.n = hi - lo;
-    q.blk0 = blk;
-    blk += (int)((q.n / 4 + in.f4_per_block - 1) / in.f4_per_block);
-    rest.p[rest.npieces++] = q;
-    return true;
+    return rest.add_piece(q);  // (no finish(): the reduce-tail launch has no GEMM blocks)
   };
   for (int i = 0; i < in.npieces; ++i) {
     const UpdPiece& p = in.p[i];
     // the spans inside this piece, in address order
     int64_t cuts[2][2];
     int nc = 0;
-    for (Span& s : sp) {
+    for (Want& s : sp) {
       const int64_t o = s.w - p.w;
       if (o + s.n <= 0 || o >= p.n) continue;       // disjoint
       if (o < 0 || o + s.n > p.n) return false;      // straddles the piece edge
-      s.pw = p.w + o; s.pm = p.m + o; s.pv = span_at(p.v, o); s.lr_t = p.lr_t;
+      s.s = p.span(o); s.step = p.step;
       cuts[nc][0] = o; cuts[nc][1] = o + s.n; ++nc;
     }
     if (nc == 2 && cuts[1][0] < cuts[0][0]) {
@@ -371,26 +365,23 @@ inline bool final_split(const Engine& e, const UpdTail& in, const PN& pn, WgradA
     }
     if (!keep(p, at, p.n)) return false;
   }
-  if (!sp[0].pw || !sp[1].pw || sp[0].lr_t != sp[1].lr_t) return false;
-  rest.nblocks = blk;
+  if (!sp[0].s.w || !sp[1].s.w || sp[0].step != sp[1].step) return false;
   static_cast<PN&>(pa) = pn;
-  pa.w_w = sp[0].pw; pa.w_m = sp[0].pm; pa.w_v = sp[0].pv;
-  pa.b_w = sp[1].pw; pa.b_m = sp[1].pm; pa.b_v = sp[1].pv;
-  pa.lr_t = sp[0].lr_t;
-  pa.c1 = in.c1; pa.c2 = in.c2; pa.eps = in.eps; pa.scale = in.scale;
-  pa.rule = in.rule; pa.mu = in.mu;
+  pa.wt = sp[0].s;
+  pa.bias = sp[1].s;
+  pa.rule = in.rule;
+  pa.step = sp[0].step;
   return true;
 }
 
-// The update spans (parameter, m, v, lr_t) of [w, w + n) inside the update pieces of `t` (v null
-// under the momentum rule).
-inline bool find_span(const UpdTail& t, const float* w, int64_t n, float*& pw, float*& pm,
-                      float*& pv, float& lr) {
+// The update span and step size of [w, w + n) inside the update pieces of `t` (v null under the
+// momentum rule).
+inline bool find_span(const UpdTail& t, const float* w, int64_t n, UpdSpan& s, float& step) {
   for (int i = 0; i < t.npieces; ++i) {
     const UpdPiece& p = t.p[i];
     const int64_t o = w - p.w;
     if (o >= 0 && o + n <= p.n) {
-      pw = p.w + o; pm = p.m + o; pv = span_at(p.v, o); lr = p.lr_t;
+      s = p.span(o); step = p.step;
       return true;
     }
   }
@@ -428,21 +419,14 @@ inline bool final_split_conv12(const Engine& e, const UpdTail& in, const PB& pb,
     }
     if (first || p.n - pos >= kPad) return false;
   }
-  float lr[4];
+  float step[4];
   static_cast<PB&>(pa) = pb;
-  if (!find_span(in, e.P[2], n2w, pa.w_w, pa.w_m, pa.w_v, lr[0]) ||
-      !find_span(in, e.P[3], n2b, pa.b_w, pa.b_m, pa.b_v, lr[1]) ||
-      !find_span(in, e.P[0], n1w, ad.w_w, ad.w_m, ad.w_v, lr[2]) ||
-      !find_span(in, e.P[1], n1b, ad.b_w, ad.b_m, ad.b_v, lr[3]))
+  if (!find_span(in, e.P[2], n2w, pa.wt, step[0]) || !find_span(in, e.P[3], n2b, pa.bias, step[1]) ||
+      !find_span(in, e.P[0], n1w, ad.wt, step[2]) || !find_span(in, e.P[1], n1b, ad.bias, step[3]))
     return false;
-  if (lr[1] != lr[0] || lr[2] != lr[0] || lr[3] != lr[0]) return false;
-  pa.lr_t = ad.lr_t = lr[0];
-  pa.c1 = ad.c1 = in.c1;
-  pa.c2 = ad.c2 = in.c2;
-  pa.eps = ad.eps = in.eps;
-  pa.scale = ad.scale = in.scale;
+  if (step[1] != step[0] || step[2] != step[0] || step[3] != step[0]) return false;
   pa.rule = ad.rule = in.rule;
-  pa.mu = ad.mu = in.mu;
+  pa.step = ad.step = step[0];
   ad.on = 1;
   return true;
 }

@@ -77,8 +77,42 @@ DDL_DEV void push_tail_body(const UpdTail& t, const UpdPiece& P, int b) {
     __hip_atomic_store(P.posted + j, t.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// One optimizer-tail block (tail.h): kTailF4PerLane float4 of one piece per lane, all loads
-// issued before any math (HBM-bound: memory-level parallelism is the whole game).
+// One optimizer-tail block (tail.h) of piece P under rule KIND: kTailF4PerLane float4 per lane,
+// all loads issued before any math (HBM-bound: memory-level parallelism is the whole game).
+// Momentum has no v stream: P.v is null and never formed.
+template <int KIND>
+DDL_DEV void upd_tail_body(const UpdTail& t, const UpdPiece& P, int b) {
+  constexpr bool kV = KIND == kUpdAdam;
+  const int64_t n4 = P.n >> 2;
+  const int64_t blk_base = (int64_t)(b - P.blk0) * t.f4_per_block + (threadIdx.x & 63);
+  float4* w = reinterpret_cast<float4*>(P.w);
+  const float4* g = reinterpret_cast<const float4*>(P.g);
+  float4* m = reinterpret_cast<float4*>(P.m);
+  float4* v = reinterpret_cast<float4*>(P.v);
+  for (int off = 0; off < t.f4_per_block; off += kTailF4PerBlock) {
+    const int64_t base = blk_base + off;
+    if (base >= n4) break;
+    float4 W[kTailF4PerLane], G[kTailF4PerLane], M[kTailF4PerLane], V[kTailF4PerLane];
+#pragma unroll
+    for (int j = 0; j < kTailF4PerLane; ++j) {
+      const int64_t e = base + j * 64;
+      if (e < n4) {
+        W[j] = w[e]; G[j] = g[e]; M[j] = m[e];
+        if constexpr (kV) V[j] = v[e];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kTailF4PerLane; ++j) {
+      const int64_t e = base + j * 64;
+      if (e >= n4) continue;
+      upd4<KIND>(t.rule, P.step, W[j], G[j], M[j], V[j]);
+      w[e] = W[j]; m[e] = M[j];
+      if constexpr (kV) v[e] = V[j];
+    }
+  }
+}
+
+// Tail block b (tail.h): find its piece, then run the tail kind's body.
 DDL_DEV void tail_body(const UpdTail& t, int b) {
   int i = 0;
 #pragma unroll
@@ -93,56 +127,9 @@ DDL_DEV void tail_body(const UpdTail& t, int b) {
       __hip_atomic_store(t.p[0].arrive, t.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     return;
   }
-  const UpdPiece& P = t.p[i];
-  const int64_t n4 = P.n >> 2;
-  const int64_t blk_base = (int64_t)(b - P.blk0) * t.f4_per_block + (threadIdx.x & 63);
-  float4* w = reinterpret_cast<float4*>(P.w);
-  const float4* g = reinterpret_cast<const float4*>(P.g);
-  float4* m = reinterpret_cast<float4*>(P.m);
-  if (t.rule == kTailMomentum) {  // wave-uniform (kernel argument): w, g, m only, P.v is null
-    for (int off = 0; off < t.f4_per_block; off += kTailF4PerBlock) {
-      const int64_t base = blk_base + off;
-      if (base >= n4) break;
-      float4 W[kTailF4PerLane], G[kTailF4PerLane], M[kTailF4PerLane];
-#pragma unroll
-      for (int j = 0; j < kTailF4PerLane; ++j) {
-        const int64_t e = base + j * 64;
-        if (e < n4) { W[j] = w[e]; G[j] = g[e]; M[j] = m[e]; }
-      }
-#pragma unroll
-      for (int j = 0; j < kTailF4PerLane; ++j) {
-        const int64_t e = base + j * 64;
-        if (e >= n4) continue;
-        momentum1(W[j].x, G[j].x, M[j].x, P.lr_t, t.mu, t.scale);
-        momentum1(W[j].y, G[j].y, M[j].y, P.lr_t, t.mu, t.scale);
-        momentum1(W[j].z, G[j].z, M[j].z, P.lr_t, t.mu, t.scale);
-        momentum1(W[j].w, G[j].w, M[j].w, P.lr_t, t.mu, t.scale);
-        w[e] = W[j]; m[e] = M[j];
-      }
-    }
-    return;
-  }
-  float4* v = reinterpret_cast<float4*>(P.v);
-  for (int off = 0; off < t.f4_per_block; off += kTailF4PerBlock) {
-    const int64_t base = blk_base + off;
-    if (base >= n4) break;
-    float4 W[kTailF4PerLane], G[kTailF4PerLane], M[kTailF4PerLane], V[kTailF4PerLane];
-#pragma unroll
-    for (int j = 0; j < kTailF4PerLane; ++j) {
-      const int64_t e = base + j * 64;
-      if (e < n4) { W[j] = w[e]; G[j] = g[e]; M[j] = m[e]; V[j] = v[e]; }
-    }
-#pragma unroll
-    for (int j = 0; j < kTailF4PerLane; ++j) {
-      const int64_t e = base + j * 64;
-      if (e >= n4) continue;
-      adam1(W[j].x, G[j].x * t.scale, M[j].x, V[j].x, P.lr_t, t.c1, t.c2, t.eps);
-      adam1(W[j].y, G[j].y * t.scale, M[j].y, V[j].y, P.lr_t, t.c1, t.c2, t.eps);
-      adam1(W[j].z, G[j].z * t.scale, M[j].z, V[j].z, P.lr_t, t.c1, t.c2, t.eps);
-      adam1(W[j].w, G[j].w * t.scale, M[j].w, V[j].w, P.lr_t, t.c1, t.c2, t.eps);
-      w[e] = W[j]; m[e] = M[j]; v[e] = V[j];
-    }
-  }
+  // the rule is wave-uniform (kernel argument): chosen once per block, one rule's loop each
+  if (t.rule.kind == kUpdMomentum) upd_tail_body<kUpdMomentum>(t, t.p[i], b);
+  else upd_tail_body<kUpdAdam>(t, t.p[i], b);
 }
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));

@@ -743,65 +743,41 @@ using WgradConv3 = ConvWgradBM<7, 64, 128>;
 using WgradConv2 = ConvWgradBM<14, 32, 64>;
 using WgradConv1 = ConvWgrad<28, 1, 32, 28>;
 
-// A ConvWgrad whose reduce epilogue also runs the optimizer (Adam, TF1 form, common.h adam1, or
-// momentum / SGD, common.h momentum1) on every element it has just summed: with one worker the update of conv1 (the step's last
+// A ConvWgrad whose reduce epilogue also runs the optimizer (update.h: Adam or momentum / SGD)
+// on every element it has just summed: with one worker the update of conv1 (the step's last
 // gradients) needs no launch of its own (gemm.h splitk_wide_reduce_tail).  The gradient is
-// still stored.  w/m/v: conv1's weight [25*CIN*COUT] and bias [COUT] parameter / Adam-state
-// spans, in the same layout as gw / gb.
+// still stored.  wt / bias: the weight [KW * COUT] and bias [COUT] parameter / optimizer-state
+// spans, in the same layout as gw / gb (v null and untouched under momentum).
 template <class P>
 struct WgradAdam : P {
-  float *w_w, *w_m, *w_v;  // weight span
-  float *b_w, *b_m, *b_v;  // bias span
-  float lr_t, c1, c2, eps, scale;
-  int rule = kTailAdam;    // tail.h: kTailMomentum applies momentum1 (w_v / b_v null, untouched)
-  float mu = 0.f;
-  // (a loop of its own, chosen once per call, so that the Adam loop below stays as it was: this
-  // is the step's last launch)
-  DDL_DEV void epi_momentum(int m0, int n, f32x4 v) const {
-    constexpr int KW = P::KW;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int m = m0 + r;
-      float *pw, *pm;
-      size_t i;
-      if (m < KW) {
-        i = (size_t)m * this->N + n; pw = w_w; pm = w_m;
-        this->gw[i] = v[r];
-      } else if (m == KW) {
-        i = (size_t)n; pw = b_w; pm = b_m;
-        this->gb[i] = v[r];
-      } else {
-        continue;
-      }
-      float W = pw[i], M = pm[i];
-      momentum1(W, v[r], M, lr_t, mu, scale);
-      pw[i] = W; pm[i] = M;
-    }
-  }
-  DDL_DEV void epi(int m0, int n, f32x4 v) const {
-    if (rule == kTailMomentum) {
-      epi_momentum(m0, n, v);
-      return;
-    }
+  UpdSpan wt, bias;
+  UpdRule rule;
+  float step;
+  // one row loop for every rule: the kind is a template argument, chosen once per call (this is
+  // the step's last launch, so no rule's loop carries a test of the kind)
+  template <int KIND>
+  DDL_DEV void epi_rows(int m0, int n, f32x4 v) const {
     constexpr int KW = P::KW;  // gw is [KW, N] (N = COUT)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int m = m0 + r;
-      float *pw, *pm, *pv;
+      UpdSpan s;
       size_t i;
       if (m < KW) {
-        i = (size_t)m * this->N + n; pw = w_w; pm = w_m; pv = w_v;
+        i = (size_t)m * this->N + n; s = wt;
         this->gw[i] = v[r];
       } else if (m == KW) {
-        i = (size_t)n; pw = b_w; pm = b_m; pv = b_v;
+        i = (size_t)n; s = bias;
         this->gb[i] = v[r];
       } else {
         continue;
       }
-      float W = pw[i], M = pm[i], V = pv[i];
-      adam1(W, v[r] * scale, M, V, lr_t, c1, c2, eps);
-      pw[i] = W; pm[i] = M; pv[i] = V;
+      upd1_at<KIND>(rule, step, s.w, v[r], s.m, s.v, i);
     }
+  }
+  DDL_DEV void epi(int m0, int n, f32x4 v) const {
+    if (rule.kind == kUpdMomentum) epi_rows<kUpdMomentum>(m0, n, v);
+    else epi_rows<kUpdAdam>(m0, n, v);
   }
 };
 

@@ -60,8 +60,9 @@ RcclAsync::RcclAsync(float* params, float* grads, int world, int rank, int devic
                      int opt, double lr, double b1, double b2, float eps, float mu,
                      bool self_sessions)
     : w_(params), g_(grads), world_(world), rank_(rank), device_(device), ranges_(ps_ranges),
-      hosts_(hosts), ps_(hosted), opt_(opt), lr_((float)lr), b1_((float)b1), b2_((float)b2),
-      eps_(eps), mu_(mu), lrd_(lr), b1d_(b1), b2d_(b2), self_(self_sessions) {
+      hosts_(hosts), ps_(hosted),
+      rule_(opt == 0 ? kUpdAdam : kUpdMomentum, (float)b1, (float)b2, eps, mu, 1.f),
+      lr_((float)lr), lrd_(lr), b1d_(b1), b2d_(b2), self_(self_sessions) {
   if (world < 1 || world > kXgmiMaxPeers) throw std::invalid_argument("rccl async: world");
   if (ranges_.size() != hosts_.size() || ranges_.empty())
     throw std::invalid_argument("rccl async: one host per PS range");
@@ -125,14 +126,9 @@ void RcclAsync::apply(int p, int worker, const float* g) {
   AsyncPsState* st = state_of(p);
   const int64_t n = ranges_[p].second - ranges_[p].first;
   const int64_t t = __atomic_add_fetch(&st->t, 1, __ATOMIC_ACQ_REL);
-  if (opt_ == 0) {
-    // TF1 Adam's lr_t in double, as ops/adam.py adam_coeffs (the same bits as the sync path)
-    const float lr_t = (float)(lrd_ * std::sqrt(1.0 - std::pow(b2d_, (double)t)) /
-                               (1.0 - std::pow(b1d_, (double)t)));
-    launch_adam(st->params, g, st->m, st->v, n, lr_t, b1_, b2_, eps_, 1.f, cs_);
-  } else {
-    launch_momentum(st->params, g, st->m, n, lr_, mu_, 1.f, cs_);
-  }
+  // TF1 Adam's lr_t from true doubles, as ops/adam.py adam_coeffs (the same bits as the sync path)
+  const float step = rule_.kind == kUpdAdam ? adam_step_size(lrd_, b1d_, b2d_, t) : lr_;
+  launch_update(rule_, step, UpdSpan{st->params, st->m, st->v}, g, n, cs_);
   const int64_t k = ++count_[(size_t)worker * ranges_.size() + p];
   if (keep_prov_) prov_.push_back({(int64_t)worker, (int64_t)p, k, t});
 }

@@ -185,7 +185,7 @@ void SyncRunner::set_units(const std::vector<RunnerUnit>& units) {
         throw std::invalid_argument("the replicated xGMI bucket must be the last segment's");
       // (an owner bucket's optimizer state exists only on its owner rank)
       const bool owns = peer_->owner(u.bucket) < 0 || peer_->owner(u.bucket) == rank_;
-      if (owns && opt_ == 0 && !u.v) throw std::invalid_argument("xGMI unit without Adam state");
+      if (owns && rule_.kind == kUpdAdam && !u.v) throw std::invalid_argument("xGMI unit without Adam state");
       if (peer_->owner(u.bucket) >= 0 && peer_->owner(u.bucket) != u.host)
         throw std::invalid_argument("xGMI owner bucket hosted on another rank than its unit");
     }
@@ -241,7 +241,7 @@ void SyncRunner::set_units(const std::vector<RunnerUnit>& units) {
     }
   coalesce(merged_);
   // tail_ok_: the shape fits for the momentum rule (w, g, m); tail_v_ok_: and every piece has a
-  // vector-shaped v, which the Adam rule needs.  Kept apart so that step() decides by opt_ at
+  // vector-shaped v, which the Adam rule needs.  Kept apart so that step() decides by the rule at
   // that time, whichever of set_optimizer / set_units came first.
   tail_ok_ = tail_v_ok_ = true;
   auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
@@ -256,38 +256,33 @@ void SyncRunner::set_units(const std::vector<RunnerUnit>& units) {
   }
 }
 
-// Segment `seg`'s update (Adam or momentum, by opt_) as the optimizer tail of the engine's next
-// dual launch.  Momentum: the step size is lr_, as in update(), and v stays null.
+// Segment `seg`'s update under the current rule as the optimizer tail of the engine's next dual
+// launch.  Momentum: the step size is lr_, as in update(), and v stays null.
 void SyncRunner::set_tail(int seg, const float* lr_t, int f4_per_block) {
   UpdTail t;
-  const bool mom = opt_ == 1;
-  t.rule = mom ? kTailMomentum : kTailAdam;
-  t.mu = mu_;
+  const bool mom = rule_.kind == kUpdMomentum;
+  t.rule = rule_;
   t.first = tail_first_;
   t.f4_per_block = f4_per_block > 0 ? f4_per_block : tail_f4_;
-  t.c1 = 1.f - b1_;
-  t.c2 = 1.f - b2_;
-  t.eps = eps_;
-  t.scale = grad_scale_;
-  int blk = 0;
   for (const auto& p : seg_pieces_[seg]) {
-    UpdPiece& q = t.p[t.npieces++];
+    UpdPiece q;
     q.w = w_ + p.r.lo;
     q.g = g_ + p.r.lo;
     q.m = p.m + p.r.state_off;
     q.v = mom ? nullptr : p.v + p.r.state_off;
     q.n = p.r.hi - p.r.lo;
-    q.lr_t = mom ? lr_ : lr_t[p.ps];
-    q.blk0 = blk;
-    blk += (int)((q.n / 4 + t.f4_per_block - 1) / t.f4_per_block);
+    q.step = step_of(lr_t[p.ps]);
+    t.add_piece(q);  // (tail_ok_: at most kTailPieces per segment)
   }
-  t.nblocks = (blk + 7) & ~7;
+  t.finish();
   eng_->tail = t;
 }
 
 void SyncRunner::set_optimizer(int kind, float lr, float b1, float b2, float eps, float mu) {
-  if (kind != 0 && kind != 1) throw std::invalid_argument("native runner: adam or momentum");
-  opt_ = kind; lr_ = lr; b1_ = b1; b2_ = b2; eps_ = eps; mu_ = mu;
+  if (kind != kUpdAdam && kind != kUpdMomentum)
+    throw std::invalid_argument("native runner: adam or momentum");
+  rule_ = UpdRule(kind, b1, b2, eps, mu, rule_.scale);
+  lr_ = lr;
 }
 
 // An update on the comm stream overlaps the backward's dual launches: fewer workgroups leave
@@ -298,12 +293,9 @@ void SyncRunner::set_optimizer(int kind, float lr, float b1, float b2, float eps
 #ifndef DDL_COMM_ADAM_GRID
 #define DDL_COMM_ADAM_GRID 128
 #endif
-void SyncRunner::update(float* w, const float* g, float* m, float* v, int64_t n, float lr_t,
-                        hipStream_t st) {
+void SyncRunner::update(const UpdSpan& s, const float* g, int64_t n, float lr_t, hipStream_t st) {
   const int max_grid = st == cs_ ? DDL_COMM_ADAM_GRID : 2048;
-  if (opt_ == 0)
-    launch_adam_c(w, g, m, v, n, lr_t, 1.f - b1_, 1.f - b2_, eps_, grad_scale_, st, max_grid);
-  else launch_momentum(w, g, m, n, lr_, mu_, grad_scale_, st, max_grid);
+  launch_update(rule_, step_of(lr_t), s, g, n, st, max_grid);
   upd_launches_ += n > 0;
 }
 
@@ -324,8 +316,7 @@ void SyncRunner::issue(const RunnerUnit& u, const float* lr_t, hipStream_t st) {
   switch (u.kind) {
     case RunnerUnit::LOCAL:
       for (const auto& r : u.ranges)
-        update(w_ + r.lo, g_ + r.lo, u.m + r.state_off, u.v ? u.v + r.state_off : nullptr,
-               r.hi - r.lo, lt, st);
+        update(span_of(r, u.m, u.v), g_ + r.lo, r.hi - r.lo, lt, st);
       break;
     case RunnerUnit::RS: {
       const auto& r = u.ranges[0];
@@ -333,7 +324,9 @@ void SyncRunner::issue(const RunnerUnit& u, const float* lr_t, hipStream_t st) {
       float* mine = w_ + r.lo + rank_ * c;
       RCCL_CHECK(rccl().ReduceScatter(g_ + r.lo, u.shard, (size_t)c, ncclFloat32, ncclSum,
                                    as_comm(comm_), st));
-      update(mine, u.shard, u.m + r.state_off, u.v ? u.v + r.state_off : nullptr, c, lt, st);
+      UpdSpan s = span_of(r, u.m, u.v);
+      s.w = mine;
+      update(s, u.shard, c, lt, st);
       RCCL_CHECK(rccl().AllGather(mine, w_ + r.lo, (size_t)c, ncclFloat32, as_comm(comm_), st));
     } break;
     case RunnerUnit::AR: {
@@ -344,7 +337,7 @@ void SyncRunner::issue(const RunnerUnit& u, const float* lr_t, hipStream_t st) {
       const int64_t n = r.hi - r.lo;
       RCCL_CHECK(rccl().AllReduce(g_ + r.lo, g_ + r.lo, (size_t)n, ncclFloat32, ncclSum,
                                   as_comm(comm_), st));
-      update(w_ + r.lo, g_ + r.lo, u.m + r.state_off, u.v ? u.v + r.state_off : nullptr, n, lt, st);
+      update(span_of(r, u.m, u.v), g_ + r.lo, n, lt, st);
     } break;
     default:
       throw std::invalid_argument("unknown unit kind");
@@ -370,8 +363,7 @@ void SyncRunner::issue_reduce_group(const std::vector<const RunnerUnit*>& us, co
   for (const RunnerUnit* u : us)
     if (rank_ == u->host)
       for (const auto& r : u->ranges)
-        update(w_ + r.lo, g_ + r.lo, u->m + r.state_off, u->v ? u->v + r.state_off : nullptr,
-               r.hi - r.lo, lr_t[u->ps], st);
+        update(span_of(r, u->m, u->v), g_ + r.lo, r.hi - r.lo, lr_t[u->ps], st);
   RCCL_CHECK(rccl().GroupStart());
   for (const RunnerUnit* u : us)
     for (const auto& r : u->ranges)
@@ -402,7 +394,8 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
     eng_->forward(x, B, seed, true, st, /*defer_fc2=*/true);  // backward_segment(0) follows
   }
   // (Adam needs every piece's v; momentum / SGD have none and form none)
-  if (all_local_ && local_on_main_ && use_tail_ && tail_ok_ && (opt_ == 1 || tail_v_ok_) &&
+  if (all_local_ && local_on_main_ && use_tail_ && tail_ok_ &&
+      (rule_.kind == kUpdMomentum || tail_v_ok_) &&
       coef_ == 1.f) {
     // segment s-1's update rides in segment s's dual launch (flushed as a launch of its own
     // if the segment had no dual launch to take it); the last segment's follows the backward
@@ -427,8 +420,7 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
     eng_->final_upd = UpdTail();
     TraceRange r("ddl.update.last_segment");
     for (const auto& p : seg_pieces_[kSegments - 1])
-      update(w_ + p.r.lo, g_ + p.r.lo, p.m + p.r.state_off, p.v ? p.v + p.r.state_off : nullptr,
-             p.r.hi - p.r.lo, lr_t[p.ps], st);
+      update(span_of(p.r, p.m, p.v), g_ + p.r.lo, p.r.hi - p.r.lo, lr_t[p.ps], st);
     return;
   }
   if (all_local_ && local_on_main_) {
@@ -440,8 +432,7 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
     if (coef_ != 1.f)
       for (const auto& p : merged_) scale_grads(g_ + p.r.lo, p.r.hi - p.r.lo, st);
     for (const auto& p : merged_)
-      update(w_ + p.r.lo, g_ + p.r.lo, p.m + p.r.state_off, p.v ? p.v + p.r.state_off : nullptr,
-             p.r.hi - p.r.lo, lr_t[p.ps], st);
+      update(span_of(p.r, p.m, p.v), g_ + p.r.lo, p.r.hi - p.r.lo, lr_t[p.ps], st);
     return;
   }
   // The last segment's gradients complete with the backward, so nothing is left to overlap
@@ -561,18 +552,12 @@ void SyncRunner::issue_xgmi(const RunnerUnit& u, const float* lr_t, bool final_w
                             hipStream_t st, bool gated) {
   XgmiUpdate up;
   const auto& r = u.ranges[0];
-  up.opt = opt_;
+  up.rule = rule_;
+  up.step = step_of(lr_t[u.ps]);
   // an owner bucket addresses its runs' state offsets itself (PeerExchange bucket spec)
   const bool own = peer_->owner(u.bucket) >= 0;
   up.m = u.m ? u.m + (own ? 0 : r.state_off) : nullptr;
   up.v = u.v ? u.v + (own ? 0 : r.state_off) : nullptr;
-  up.lr_t = lr_t[u.ps];
-  up.c1 = 1.f - b1_;
-  up.c2 = 1.f - b2_;
-  up.eps = eps_;
-  up.lr = lr_;
-  up.mu = mu_;
-  up.scale = grad_scale_;
   up.coef = coef_;
   peer_->launch(u.bucket, epoch_, up, final_wait, st, gated);
 }
@@ -581,7 +566,7 @@ void SyncRunner::peer_selftest_step(hipStream_t st) {
   if (!peer_) throw std::runtime_error("no PeerExchange");
   ++epoch_;
   XgmiUpdate up;
-  up.opt = 2;
+  up.rule.kind = kUpdCopy;
   const int nb = peer_->num_buckets();
   for (int b = 0; b < nb; ++b) peer_->launch(b, epoch_, up, b == nb - 1, st);
 }

@@ -8,7 +8,9 @@
 // run as extra blocks of segment s+1's dual dgrad+wgrad launch: memory-bound blocks beside
 // MFMA-bound ones, hidden instead of serialised.  Only the last segment's (conv1 + conv2,
 // 52 k parameters) update remains a launch of its own.  Momentum and plain SGD take the same
-// slots (UpdTail::rule): w, g, m only, so 5 streams instead of 7 and no v anywhere.
+// slots (UpdTail::rule, update.h): w, g, m only, so 5 streams instead of 7 and no v anywhere.
+// The tail body (gemm.h tail_body) is one loop templated on the rule's kind, entered through a
+// wave-uniform choice made once per block.
 //
 // The asynchronous worker step (async_runner.hip) uses the same slot for its gradient PUSH
 // (kind 1): segment s's shards are stored into their PS hosts' inboxes and posted on the
@@ -22,6 +24,8 @@
 // pair (~5 us of idle compute stream each, runner.hip).
 #pragma once
 #include <stdint.h>
+
+#include "update.h"
 
 namespace ddl {
 
@@ -40,7 +44,7 @@ struct UpdPiece {
   float* m = nullptr;
   float* v = nullptr;      // null under the momentum rule
   int64_t n = 0;           // elements
-  float lr_t = 0.f;        // TF1 Adam step size of the owning PS (momentum: the learning rate)
+  float step = 0.f;        // update.h: TF1 Adam's lr_t of the owning PS, or the learning rate
   int blk0 = 0;            // first tail block of this piece
   // push (kind 1): slice j = block blk0 + j covers float4 [j * slice4, (j + 1) * slice4); its
   // board word posted[j] (host memory).  Ready flag
@@ -48,24 +52,33 @@ struct UpdPiece {
   uint32_t* arrive = nullptr;
   uint32_t* posted = nullptr;
   int slice4 = 0, nslice = 0;
+  UpdSpan span(int64_t off) const { return UpdSpan{w, m, v}.at(off); }
 };
-
-constexpr int kTailAdam = 0, kTailMomentum = 1;  // UpdTail::rule
 
 struct UpdTail {
   int nblocks = 0;         // tail blocks (multiple of 8: keeps the GEMM blocks' XCD mapping)
   int npieces = 0;
-  int kind = 0;            // 0: update (`rule`), 1: asynchronous gradient push (round `epoch`),
+  int kind = 0;            // 0: update by `rule`, 1: asynchronous gradient push (round `epoch`),
                            // 2: ready flag (p[0].arrive[0] = epoch)
   uint32_t epoch = 0;
   int first = 1;           // 1: tail blocks precede the GEMM blocks in the grid, 0: follow them
   int f4_per_block = kTailF4PerBlock;  // float4 per tail block (multiple of kTailF4PerBlock)
   UpdPiece p[kTailPieces];
-  float c1 = 0.f, c2 = 0.f, eps = 0.f, scale = 1.f;  // 1 - beta1, 1 - beta2, epsilon, grad scale
-  // kind 0's update rule: kTailAdam, or kTailMomentum (common.h momentum1; mu = 0: plain SGD):
-  // the pieces' v is null and never formed, lr_t is the plain learning rate
-  int rule = kTailAdam;
-  float mu = 0.f;
+  // kind 0's update rule (Adam or momentum; under momentum the pieces' v is null and never
+  // formed); each piece carries its own step size
+  UpdRule rule;
+
+  // Append update piece `q` at the next free tail block; false when the tail is full.  finish()
+  // after the last piece.  (n % 4 == 0 for a tail that rides in a launch; flush_tail takes any n)
+  bool add_piece(UpdPiece q) {
+    if (npieces >= kTailPieces) return false;
+    q.blk0 = nblocks;
+    nblocks += (int)((q.n / 4 + f4_per_block - 1) / f4_per_block);
+    p[npieces++] = q;
+    return true;
+  }
+  // a tail beside GEMM blocks: pad to a multiple of 8 blocks (their XCD mapping stays)
+  void finish() { nblocks = (nblocks + 7) & ~7; }
 };
 
 }  // namespace ddl

@@ -130,28 +130,6 @@ DDL_DEV void final_wait(const XgmiLaunch& a, const uint32_t* myflags, int W, lon
                 gridDim.x * 256);
 }
 
-// The owner-side optimizer update of one float4 (TF1 Adam, momentum, or the self-test's
-// w := g), shared by the owner kernel and the replicated kernel so both give the same bits.
-DDL_DEV void update4(const XgmiLaunch& a, float4& w, float4 g, float4* m4, float4* v4, int i) {
-  if (a.opt == 0) {  // TF1 Adam (optim.hip form)
-    float4 M = m4[i], V = v4[i];
-    adam1(w.x, g.x * a.scale, M.x, V.x, a.lr_t, a.c1, a.c2, a.eps);
-    adam1(w.y, g.y * a.scale, M.y, V.y, a.lr_t, a.c1, a.c2, a.eps);
-    adam1(w.z, g.z * a.scale, M.z, V.z, a.lr_t, a.c1, a.c2, a.eps);
-    adam1(w.w, g.w * a.scale, M.w, V.w, a.lr_t, a.c1, a.c2, a.eps);
-    m4[i] = M; v4[i] = V;
-  } else if (a.opt == 1) {  // momentum SGD (optim.hip momentum_kernel form)
-    float4 M = m4[i];
-    momentum1(w.x, g.x, M.x, a.lr, a.mu, a.scale);
-    momentum1(w.y, g.y, M.y, a.lr, a.mu, a.scale);
-    momentum1(w.z, g.z, M.z, a.lr, a.mu, a.scale);
-    momentum1(w.w, g.w, M.w, a.lr, a.mu, a.scale);
-    m4[i] = M;
-  } else {  // self-test: parameters := the summed gradient
-    w = g;
-  }
-}
-
 // WT = world size when instantiated for it (loops over ranks fully unrolled: all of an
 // element's remote loads / stores are in flight together), 0 = any world size.
 template <int WT>
@@ -251,7 +229,7 @@ __global__ void __launch_bounds__(256) xgmi_ps_kernel(XgmiTable T, XgmiLaunch a)
 #pragma unroll
     for (int q = 0; q < NQ; ++q)  // rank order: the same sum on every run and every rank count
       if (q < W) { g.x += x[q].x; g.y += x[q].y; g.z += x[q].z; g.w += x[q].w; }
-    update4(a, w, g, m4, v4, i);
+    upd4_any(a.rule, a.step, w, g, m4, v4, i);
     // every rank's copy, this one included: write-through, so a later kernel of any rank
     // (other XCD, other GPU) reads it from memory even while this kernel is still running
 #pragma unroll
@@ -356,7 +334,7 @@ __global__ void __launch_bounds__(256) xgmi_repl_kernel(XgmiTable T, XgmiLaunch 
     for (int q = 0; q < NQ; ++q)  // rank order, as the owner kernel: identical bits
       if (q < W) { g.x += x[q].x; g.y += x[q].y; g.z += x[q].z; g.w += x[q].w; }
     float4 w = w4[i];
-    update4(a, w, g, m4, v4, i);
+    upd4_any(a.rule, a.step, w, g, m4, v4, i);
     w4[i] = w;  // this rank's copy only (the next forward is a later kernel of this stream)
   }
   if (a.final_wait) final_wait(a, myflags, W, deadline);
@@ -454,7 +432,7 @@ __global__ void __launch_bounds__(256) xgmi_owner_kernel(XgmiTable T, XgmiLaunch
 #pragma unroll
     for (int q = 0; q < NQ; ++q)  // rank order, as the RCCL reduce and xgmi_ps_kernel
       if (q < W) { g.x += x[q].x; g.y += x[q].y; g.z += x[q].z; g.w += x[q].w; }
-    update4(a, w, g, m4, v4, i);
+    upd4_any(a.rule, a.step, w, g, m4, v4, i);
 #pragma unroll
     for (int k = 0; k < NQ; ++k) {
       if (k < W) {
@@ -675,8 +653,9 @@ void PeerExchange::fill(int bucket, uint32_t epoch, const XgmiUpdate& u, bool fi
   if (bucket < 0 || bucket >= (int)bk_.size()) throw std::invalid_argument("xgmi: bucket index");
   const Bucket& B = bk_[bucket];
   const bool owns = B.owner < 0 || B.owner == rank_;  // runs the update of (part of) the bucket
-  if (owns && u.opt != 2 && !u.m) throw std::invalid_argument("xgmi: optimizer state missing");
-  if (owns && u.opt == 0 && !u.v) throw std::invalid_argument("xgmi: Adam needs v");
+  if (owns && u.rule.kind != kUpdCopy && !u.m)
+    throw std::invalid_argument("xgmi: optimizer state missing");
+  if (owns && u.rule.kind == kUpdAdam && !u.v) throw std::invalid_argument("xgmi: Adam needs v");
   memset(&a, 0, sizeof(a));
   a.world = world_;
   a.rank = rank_;
@@ -693,14 +672,8 @@ void PeerExchange::fill(int bucket, uint32_t epoch, const XgmiUpdate& u, bool fi
   a.grads = grads_;
   a.m = u.m;
   a.v = u.v;
-  a.opt = u.opt;
-  a.lr_t = u.lr_t;
-  a.c1 = u.c1;
-  a.c2 = u.c2;
-  a.eps = u.eps;
-  a.lr = u.lr;
-  a.mu = u.mu;
-  a.scale = u.scale;
+  a.rule = u.rule;
+  a.step = u.step;
   a.coef = u.coef;
   a.err = err_;
   a.timeout_ticks = (long long)(timeout_s_ * 1e8);  // wall_clock64: 100 MHz

@@ -165,8 +165,8 @@ struct ApplyArgs {
   float* ps_params;  // the PS's private parameter copy of its shard [n]
   float* m;
   float* v;
-  int opt;
-  float lr_t, c1, c2, eps, lr, mu, scale;
+  UpdRule rule;      // update.h (kUpdCopy: the self-test, the PS shard := the pushed gradient)
+  float step;
 };
 
 // Slice j of one apply.  No arrival poll: the apply runs only after every slice of the push was
@@ -190,23 +190,7 @@ DDL_DEV void apply_body(const AsyncTable& T, const ApplyArgs& a, int j) {
   for (int i = tid; i < n4; i += 256) {
     const float4 g = bload4_sys(in, i * 16);
     float4 w = w4[i];
-    if (a.opt == 0) {
-      float4 M = m4[i], V = v4[i];
-      adam1(w.x, g.x * a.scale, M.x, V.x, a.lr_t, a.c1, a.c2, a.eps);
-      adam1(w.y, g.y * a.scale, M.y, V.y, a.lr_t, a.c1, a.c2, a.eps);
-      adam1(w.z, g.z * a.scale, M.z, V.z, a.lr_t, a.c1, a.c2, a.eps);
-      adam1(w.w, g.w * a.scale, M.w, V.w, a.lr_t, a.c1, a.c2, a.eps);
-      m4[i] = M; v4[i] = V;
-    } else if (a.opt == 1) {
-      float4 M = m4[i];
-      momentum1(w.x, g.x, M.x, a.lr, a.mu, a.scale);
-      momentum1(w.y, g.y, M.y, a.lr, a.mu, a.scale);
-      momentum1(w.z, g.z, M.z, a.lr, a.mu, a.scale);
-      momentum1(w.w, g.w, M.w, a.lr, a.mu, a.scale);
-      m4[i] = M;
-    } else {  // self-test: the PS shard := the pushed gradient
-      w = g;
-    }
+    upd4_any(a.rule, a.step, w, g, m4, v4, i);
     w4[i] = w;
     bstore4_sys(out, i * 16, w);
   }
@@ -614,8 +598,9 @@ void AsyncPeer::apply(int ps, int worker, uint32_t epoch, const XgmiUpdate& u, f
   if (ps < 0 || ps >= nps_ || table_.shard[ps].host != rank_)
     throw std::invalid_argument("async xgmi: apply on a PS this rank does not host");
   if (worker < 0 || worker >= world_) throw std::invalid_argument("async xgmi: worker");
-  if (u.opt != 2 && !u.m) throw std::invalid_argument("async xgmi: optimizer state missing");
-  if (u.opt == 0 && !u.v) throw std::invalid_argument("async xgmi: Adam needs v");
+  if (u.rule.kind != kUpdCopy && !u.m)
+    throw std::invalid_argument("async xgmi: optimizer state missing");
+  if (u.rule.kind == kUpdAdam && !u.v) throw std::invalid_argument("async xgmi: Adam needs v");
   ApplyArgs a;
   memset(&a, 0, sizeof(a));
   a.me = rank_;
@@ -625,14 +610,8 @@ void AsyncPeer::apply(int ps, int worker, uint32_t epoch, const XgmiUpdate& u, f
   a.ps_params = ps_params;
   a.m = u.m;
   a.v = u.v;
-  a.opt = u.opt;
-  a.lr_t = u.lr_t;
-  a.c1 = u.c1;
-  a.c2 = u.c2;
-  a.eps = u.eps;
-  a.lr = u.lr;
-  a.mu = u.mu;
-  a.scale = u.scale;
+  a.rule = u.rule;
+  a.step = u.step;
   hipLaunchKernelGGL(async_apply_kernel, dim3(table_.shard[ps].nslice), dim3(256), 0, st,
                      table_dev_, a);
   DDL_CHECK_LAUNCH();
@@ -659,8 +638,8 @@ AsyncService::AsyncService(AsyncPeer* peer, int world, int device,
                            const std::vector<AsyncPsState>& ps, int opt, float lr, float b1,
                            float b2, float eps, float mu, float scale, uint32_t epoch0,
                            bool provenance)
-    : peer_(peer), world_(world), device_(device), ps_(ps), opt_(opt), lr_(lr), b1_(b1),
-      b2_(b2), eps_(eps), mu_(mu), scale_(scale), keep_prov_(provenance) {
+    : peer_(peer), world_(world), device_(device), ps_(ps),
+      rule_(opt, b1, b2, eps, mu, scale), lr_(lr), b1_(b1), b2_(b2), keep_prov_(provenance) {
   if (world < 1 || world > kXgmiMaxPeers) throw std::invalid_argument("async service: world");
   for (const auto& s : ps)
     if (s.ps < 0 || s.ps >= peer->num_ps() || !s.params || !s.m || (opt == 0 && !s.v))
@@ -703,18 +682,10 @@ void AsyncService::serve(AsyncPsState& st, int w) {
   // one apply_gradients of this PS per arrival
   const int64_t t = __atomic_add_fetch(&st.t, 1, __ATOMIC_ACQ_REL);
   XgmiUpdate u;
-  u.opt = opt_;
+  u.rule = rule_;
+  u.step = rule_.kind == kUpdMomentum ? lr_ : adam_step_size(lr_, b1_, b2_, t);
   u.m = st.m;
   u.v = st.v;
-  // TF1 Adam: lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t) (ops/adam.py adam_coeffs)
-  u.lr_t = (float)((double)lr_ * std::sqrt(1.0 - std::pow((double)b2_, (double)t)) /
-                   (1.0 - std::pow((double)b1_, (double)t)));
-  u.c1 = 1.f - b1_;
-  u.c2 = 1.f - b2_;
-  u.eps = eps_;
-  u.lr = lr_;
-  u.mu = mu_;
-  u.scale = scale_;
   peer_->apply(p, w, e, u, st.params, stream_);
   if (keep_prov_) prov_.push_back({(int64_t)w, (int64_t)p, (int64_t)e, t});
   served_.fetch_add(1);

@@ -1,6 +1,7 @@
 """CPU numerics: dropout RNG, TF1 Adam, glorot init, model oracle, quirk coefficients."""
 import math
 
+import numpy as np
 import pytest
 import torch
 
@@ -71,6 +72,26 @@ def test_tf1_adam_matches_closed_form():
     exp = torch.tensor([1.0, -2.0]) - lr_t * (0.1 * g) / ((0.001 * g * g).sqrt() + 1e-8)
     assert torch.allclose(w, exp, atol=1e-9)
     assert adam_coeffs(h, 1) == pytest.approx(lr_t)
+
+
+def test_native_adam_step_size_matches_python_bitwise():
+    """update.h adam_step_size, the one C++ copy of TF1's lr_t, against ops/adam.py adam_coeffs
+    for both operand conventions its callers use: true doubles (the RCCL async PS, as Python),
+    and float32 hyper-parameters widened to double (the xGMI async PS and the in-line runner).
+    Bit for bit as float32, t = 1 .. 2000."""
+    from ddl_amd.ops import native
+    if not native.available():
+        pytest.skip(native.error())
+    step = native.ops().adam_step_size
+    f32 = lambda x: float(np.float32(x))
+    lr, b1, b2 = 1e-4, 0.9, 0.999
+    lr32, b132, b232 = f32(lr), f32(b1), f32(b2)
+    assert (lr32, b132, b232) != (lr, b1, b2)  # the two conventions are different operands
+    h = AdamHyper(lr=lr, beta1=b1, beta2=b2)
+    for t in range(1, 2001):
+        assert step(lr, b1, b2, t) == f32(adam_coeffs(h, t)), t
+        widened = lr32 * math.sqrt(1.0 - b232 ** t) / (1.0 - b132 ** t)
+        assert step(lr32, b132, b232, t) == f32(widened), t
 
 
 def test_ps_step_counter_per_server():
