@@ -317,10 +317,43 @@ class PyPeer {
     p_->open(handles);
   }
   int error() const { return p_->error(); }
+  // One bucket's exchange kernel on the current stream, as the runner launches it but with no
+  // READY gate ahead: the kernels alone, on any small plan (tests/test_exchange_kernels_gpu.py).
+  // kind: update.h's rule kind; step: Adam's lr_t, or the learning rate.  m and v are this rank's
+  // state of the bucket (an owner bucket: the PS's, indexed by the runs' state offsets) and may be
+  // None where the rule, or a rank that does not own the bucket, has none.
+  void launch(int64_t bucket, int64_t epoch, int64_t kind, c10::optional<at::Tensor> m,
+              c10::optional<at::Tensor> v, double step, double b1, double b2, double eps,
+              double mu, double scale, double coef, bool final_wait) {
+    TORCH_CHECK(bucket >= 0 && bucket < p_->num_buckets(), "bucket out of range");
+    TORCH_CHECK(kind >= 0 && kind <= 2, "update: rule kind");
+    ddl::XgmiUpdate u;
+    u.rule = ddl::UpdRule((int)kind, (float)b1, (float)b2, (float)eps, (float)mu, (float)scale);
+    u.step = (float)step;
+    u.coef = (float)coef;
+    auto state = [&](const at::Tensor& t, const char* name) {
+      check_f32_cuda(t, name);
+      TORCH_CHECK(t.device() == params_.device(), name, " must be on the parameters' device");
+      TORCH_CHECK(t.numel() >= p_->state_extent((int)bucket), name,
+                  " is shorter than the bucket's state");
+      TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr<float>()) % 16 == 0, name,
+                  " must be 16-B aligned");
+      return t.data_ptr<float>();
+    };
+    if (m) u.m = state(*m, "m");
+    if (v) u.v = state(*v, "v");
+    c10::hip::HIPGuard guard(params_.device().index());
+    p_->launch((int)bucket, (uint32_t)epoch, u, final_wait, cur_stream());
+  }
   std::vector<int64_t> nslices() const {
     std::vector<int64_t> v;
     for (int b = 0; b < p_->num_buckets(); ++b) v.push_back(p_->nslices(b));
     return v;
+  }
+  void unmap_peers() {
+    c10::hip::HIPGuard guard(params_.device().index());
+    py::gil_scoped_release nogil;
+    p_->unmap_peers();
   }
   void close() {
     c10::hip::HIPGuard guard(params_.device().index());
@@ -385,6 +418,11 @@ class PyAsyncPeer {
     if (m) { check_f32_cuda(*m, "m"); u.m = m->data_ptr<float>(); }
     if (v) { check_f32_cuda(*v, "v"); u.v = v->data_ptr<float>(); }
     p_->apply((int)ps, (int)worker, (uint32_t)epoch, u, ps_params.data_ptr<float>(), cur_stream());
+  }
+  void unmap_peers() {
+    c10::hip::HIPGuard guard(params_.device().index());
+    py::gil_scoped_release nogil;
+    p_->unmap_peers();
   }
   void close() {
     c10::hip::HIPGuard guard(params_.device().index());
@@ -870,6 +908,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("attach_done", &PyAsyncPeer::attach_done)
       .def("wait_done", &PyAsyncPeer::wait_done)
       .def("apply", &PyAsyncPeer::apply)
+      .def("unmap_peers", &PyAsyncPeer::unmap_peers)
       .def("close", &PyAsyncPeer::close)
       .def("error", &PyAsyncPeer::error);
 
@@ -927,6 +966,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("error", &PyPeer::error)
       .def("nslices", &PyPeer::nslices)
       .def("owner", &PyPeer::owner)
+      .def("launch", &PyPeer::launch, py::arg("bucket"), py::arg("epoch"), py::arg("kind"),
+           py::arg("m"), py::arg("v"), py::arg("step"), py::arg("b1"), py::arg("b2"),
+           py::arg("eps"), py::arg("mu"), py::arg("scale"), py::arg("coef"),
+           py::arg("final_wait"))
+      .def("unmap_peers", &PyPeer::unmap_peers)
       .def("close", &PyPeer::close);
 
   py::class_<ddl::ShmMailbox>(m, "ShmMailbox")

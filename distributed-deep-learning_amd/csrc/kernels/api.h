@@ -330,11 +330,23 @@ class PeerExchange {
   void set_gate_error(const int* w) { gate_err_ = w; }
   // unmap the peers' buffers and free this rank's (after the device has drained); idempotent
   void close();
+  // the first half of close() alone.  HIP leaves freeing an exported buffer undefined while a
+  // peer still has it mapped, so a process that goes on to build another exchange lets every
+  // rank unmap first: unmap_peers(), a host barrier, close().  Nothing can be launched after it.
+  void unmap_peers();
   double timeout_s() const { return timeout_s_; }
   int num_buckets() const { return (int)bk_.size(); }
   int nslices(int b) const { return bk_[b].nslice; }
   int64_t chunk(int b) const { return bk_[b].c; }
   int owner(int b) const { return bk_[b].owner; }
+  // elements of optimizer state a launch of bucket b may touch: [0, state_extent(b)) of m and v
+  int64_t state_extent(int b) const {
+    const Bucket& B = bk_[b];
+    int64_t n = B.owner >= 0 ? 0 : B.c;
+    for (size_t r = 0; r < B.run_soff.size(); ++r)
+      if (B.run_soff[r] + B.run_n[r] > n) n = B.run_soff[r] + B.run_n[r];
+    return n;
+  }
   int world() const { return world_; }
   int repl_bucket() const { return repl_; }
   bool check_mode() const { return check_; }
@@ -404,6 +416,7 @@ class AsyncPeer {
   std::string handle() const;
   void open(const std::vector<std::string>& handles);
   void close();  // unmap peers, free buffers and the shm board (after a device drain); idempotent
+  void unmap_peers();  // the first half of close() alone (PeerExchange::unmap_peers)
   // worker: every PS shard of the gradient (x coef) into its host's inbox slot, round `epoch`
   void push_all(uint32_t epoch, float coef, hipStream_t st);
   // the same for the listed PS only (one launch); with_gate: plus the pull gate of round

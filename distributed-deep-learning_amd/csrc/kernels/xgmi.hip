@@ -516,7 +516,8 @@ void PeerExchange::init(const std::vector<XgmiBucketSpec>& buckets, int max_slic
       int64_t n = 0;
       for (size_t r = 0; r < sp.runs.size(); ++r) {
         const int64_t lo = sp.runs[r].first, hi = sp.runs[r].second;
-        if (lo < 0 || hi > total_ || hi <= lo || (hi - lo) % 4 || lo % 4 || sp.state_offs[r] % 4)
+        if (lo < 0 || hi > total_ || hi <= lo || (hi - lo) % 4 || lo % 4 || sp.state_offs[r] % 4 ||
+            sp.state_offs[r] < 0)
           throw std::invalid_argument("xgmi: owner-bucket run out of range or not 16-B shaped");
         n += hi - lo;
       }
@@ -587,8 +588,8 @@ void PeerExchange::init(const std::vector<XgmiBucketSpec>& buckets, int max_slic
 
 PeerExchange::~PeerExchange() { close(); }
 
-void PeerExchange::close() {
-  if (inbox_ || flags_ || opened_ok_) (void)hipDeviceSynchronize();
+void PeerExchange::unmap_peers() {
+  if (opened_ok_) (void)hipDeviceSynchronize();
   for (int q = 0; q < world_; ++q) {
     if (q == rank_) continue;
     for (void*& p : opened_[q]) {
@@ -597,6 +598,11 @@ void PeerExchange::close() {
     }
   }
   opened_ok_ = false;
+}
+
+void PeerExchange::close() {
+  if (inbox_ || flags_ || opened_ok_) (void)hipDeviceSynchronize();
+  unmap_peers();
   if (inbox_) (void)hipFree(inbox_);
   if (flags_) (void)hipFree(flags_);
   if (err_) (void)hipHostFree(err_);

@@ -348,8 +348,8 @@ AsyncPeer::AsyncPeer(float* params, const float* grads, int64_t total, int world
 
 AsyncPeer::~AsyncPeer() { close(); }
 
-void AsyncPeer::close() {
-  if (inbox_ || flags_ || opened_ok_) (void)hipDeviceSynchronize();
+void AsyncPeer::unmap_peers() {
+  if (opened_ok_) (void)hipDeviceSynchronize();
   for (int q = 0; q < world_; ++q) {
     if (q == rank_) continue;
     for (void*& p : opened_[q]) {
@@ -358,6 +358,11 @@ void AsyncPeer::close() {
     }
   }
   opened_ok_ = false;
+}
+
+void AsyncPeer::close() {
+  if (inbox_ || flags_ || opened_ok_) (void)hipDeviceSynchronize();
+  unmap_peers();
   if (inbox_) (void)hipFree(inbox_);
   if (flags_) (void)hipFree(flags_);
   if (err_) (void)hipHostFree(err_);
