@@ -69,9 +69,9 @@ def rank_order_sum(grads_by_rank, coef=1.0):
     return acc
 
 
-def rule_step(kind, w, m, v, g, step, mu=0.0, scale=1.0):
+def rule_step(kind, w, m, v, g, step, mu=0.0, scale=1.0, b1=B1, b2=B2, eps=EPS):
     """(w', m', v') in fp64 after one step from fp32 (or fp64) w, m, v, g; m / v pass through
-    where the rule has none."""
+    where the rule has none.  b1, b2, eps: Adam's, by default the decimal values."""
     d = lambda t: None if t is None else t.detach().double().cpu()  # noqa: E731
     w, m, v, g = d(w), d(m), d(v), d(g)
     if kind == COPY:
@@ -80,9 +80,9 @@ def rule_step(kind, w, m, v, g, step, mu=0.0, scale=1.0):
         w2, m2 = momentum_closed_form(w, m, [g], step, mu, scale)
         return w2, m2, v
     gs = g * scale
-    m2 = m + (gs - m) * (1 - B1)
-    v2 = v + (gs * gs - v) * (1 - B2)
-    return w - step * m2 / (v2.sqrt() + EPS), m2, v2
+    m2 = m + (gs - m) * (1 - b1)
+    v2 = v + (gs * gs - v) * (1 - b2)
+    return w - step * m2 / (v2.sqrt() + eps), m2, v2
 
 
 # ---- geometry: the host arithmetic of PeerExchange::init and AsyncPeer's constructor ------------

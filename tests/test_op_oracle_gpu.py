@@ -21,19 +21,11 @@ import torch
 import op_reference as R
 from ddl_amd.models.layout import CANON_OFFSETS, TOTAL_NUMEL
 from ddl_amd.models.mnist_cnn import init_params_, param_views
+from oracle_common import (BATCHES, BMAX, DEV, HALO_BUFS, HEAD_MARGIN, KEEP, SEED, bits, check,
+                           make_real_params, prepare)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-BMAX = 40
-KEEP = 0.5
-SEED = 20240
-BATCHES = (1, 5, 33)
-FLOAT_BUFS = ["p1", "p2", "p3", "p4", "h1", "h2", "dlog", "loss", "dpre2fc", "dpre1fc", "d4", "d3",
-              "d2", "d1"]
-HALO_BUFS = ("p1", "p2", "p3", "d4", "d3", "d2")
-CODE_BUFS = ["c1", "c2", "c3", "c4"]
-CODE_SENTINEL = 0x77   # not a code any kernel writes
 WIDE_INLAUNCH, WIDE_SEPARATE = 1 << 20, 1
 
 
@@ -46,6 +38,7 @@ class Ctx:
         self.P64 = [p.double() for p in P]
         self.params = torch.zeros(TOTAL_NUMEL, device=DEV)
         self.grads = torch.zeros_like(self.params)
+        self.offsets = CANON_OFFSETS
         self.eng = HipEngine(self.params, self.grads, CANON_OFFSETS, batch=BMAX, graph=False,
                              eval_chunk=BMAX, keep_prob=KEEP)
         # in place: the engine holds pointers into the flat tensor
@@ -65,6 +58,9 @@ class Ctx:
     def gview(self, i):
         return param_views(self.grads, CANON_OFFSETS)[i]
 
+    def poison_grads(self):
+        self.grads.fill_(float("nan"))
+
     def case(self, op, B, train=True, real=False):
         """(inputs, fp64 reference outputs) of op at batch B, computed once: the reference is
         exact, so every config shares it."""
@@ -73,81 +69,6 @@ class Ctx:
             inp = R.make_inputs(op, B, 1, real)
             self.cases[key] = (inp, R.run_op(op, self.P64, inp, SEED, KEEP, train))
         return self.cases[key]
-
-
-def interior(name, t):
-    return t[:, 2:-2, 2:-2, :] if name in HALO_BUFS else t
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t.contiguous()
-
-
-def prepare(ctx, B, inputs):
-    """Poison every float buffer and the gradients with NaN (all 40 rows, interiors only), put the
-    code sentinel in rows < B and 0 in rows >= B, write the inputs of rows < B; returns the image
-    argument and a snapshot of everything."""
-    nan = float("nan")
-    for n in FLOAT_BUFS:
-        interior(n, ctx.whole(n)).fill_(nan)
-    ctx.grads.fill_(nan)
-    for n in CODE_BUFS:
-        c = ctx.whole(n)
-        c[:B] = CODE_SENTINEL
-        c[B:] = 0
-    x = torch.full((B, 784), nan, device=DEV)
-    for name, v in inputs.items():
-        if name == "x":
-            x = v.to(DEV).reshape(B, 784).contiguous()
-        else:
-            dst = interior(name, ctx.whole(name))[:B]
-            dst.copy_(v.to(DEV).reshape(dst.shape))
-    snap = {n: bits(ctx.whole(n)).clone() for n in FLOAT_BUFS + CODE_BUFS}
-    snap["grads"] = bits(ctx.grads).clone()
-    return x, snap
-
-
-def check(ctx, B, snap, ref, tag, compare=None, ignore=()):
-    """Outputs `ref` (name -> fp64 / uint8 reference of rows < B) against the engine's buffers;
-    everything else against the snapshot.  `compare(name, got, ref64)` replaces torch.equal
-    for the real-valued checks; buffers in `ignore` are outputs that are not compared.  Returns
-    the list of failures."""
-    fails = []
-    touched = torch.zeros(TOTAL_NUMEL, dtype=torch.bool, device=DEV)
-    for name, want in ref.items():
-        if name.startswith("g"):
-            i = int(name[1:])
-            got = ctx.gview(i)
-            o = CANON_OFFSETS[i]
-            touched[o:o + got.numel()] = True
-            if compare is not None:
-                fails += compare(name, got.cpu(), want.reshape(got.shape))
-            elif not torch.equal(got, want.to(torch.float32).to(DEV).reshape(got.shape)):
-                fails.append(f"{tag}: {name} differs from the reference")
-            continue
-        whole = ctx.whole(name)
-        if not torch.equal(bits(whole[B:]), snap[name][B:]):
-            fails.append(f"{tag}: {name} rows >= {B} changed")
-        got = interior(name, whole)[:B]
-        if name.startswith("c"):
-            if not torch.equal(got, want.to(DEV).reshape(got.shape)):
-                fails.append(f"{tag}: codes {name} differ from the reference")
-        elif compare is not None:
-            fails += compare(name, got.cpu(), want.reshape(got.shape))
-        elif not torch.equal(got, want.to(torch.float32).to(DEV).reshape(got.shape)):
-            fails.append(f"{tag}: {name} differs from the reference")
-        if name in HALO_BUFS:
-            border = whole[:B].clone()
-            border[:, 2:-2, 2:-2, :] = 0
-            if int(torch.count_nonzero(border)) != 0:
-                fails.append(f"{tag}: halo of {name} written")
-    for n in FLOAT_BUFS + CODE_BUFS:
-        if n not in ref and n not in ignore and not torch.equal(bits(ctx.whole(n)), snap[n]):
-            fails.append(f"{tag}: {n} is not an output and changed")
-    g = bits(ctx.grads)
-    if not torch.equal(g[~touched], snap["grads"][~touched]):
-        fails.append(f"{tag}: a gradient that is not an output changed")
-    return fails
 
 
 def run_case(ctx, op, B, tag, train=True):
@@ -422,9 +343,6 @@ def head_inputs(P, B, gen, extreme_rows):
     return h2, labels, extreme
 
 
-HEAD_MARGIN = 8.0
-
-
 @pytest.mark.parametrize("kernel", ["fused", "fwd_bwd"])
 @pytest.mark.parametrize("keep", [0.5, 1.0])
 @pytest.mark.parametrize("B", [1, 33])
@@ -496,14 +414,6 @@ def test_head_matches_reference(B, keep, kernel):
     finally:
         c.eng.set_concurrent(False)
     assert not fails, "\n".join(fails)
-
-
-def make_real_params():
-    flat = torch.zeros(TOTAL_NUMEL)
-    init_params_(flat, CANON_OFFSETS, seed=8)
-    gen = torch.Generator().manual_seed(12)
-    return [p.clone() + (0.05 * torch.randn(p.shape, generator=gen) if p.dim() == 1 else 0)
-            for p in param_views(flat, CANON_OFFSETS)]
 
 
 def test_slab_sized_for_every_smaller_batch():
