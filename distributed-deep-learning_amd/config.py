@@ -26,6 +26,8 @@ class TrainConfig:
     lr: float = 1e-4
     optimizer: str = "adam"         # adam | momentum | sgd
     momentum: float = 0.9
+    weight_decay: float = 0.0       # decoupled (AdamW / SGDW): w -= lr * wd * w before each update
+    nesterov: bool = False          # momentum only: step along mu * m' + g
     keep_prob: float = 0.5
     eval_every: int = 10            # 0 disables periodic eval
     data: str = "synthetic"
@@ -54,8 +56,22 @@ class TrainConfig:
     quiet: bool = False
     watchdog_s: float = 600.0
 
+    def __post_init__(self):
+        check_optimizer_options(self.optimizer, self.momentum, self.weight_decay, self.nesterov)
+
     def to_dict(self):
         return asdict(self)
+
+
+def check_optimizer_options(optimizer: str, momentum: float, weight_decay: float,
+                            nesterov: bool) -> None:
+    """Refuse the combinations no update rule implements."""
+    if weight_decay < 0.0:
+        raise ValueError(f"--weight-decay must not be negative (got {weight_decay})")
+    if nesterov and optimizer != "momentum":
+        raise ValueError(f"--nesterov needs --optimizer momentum (got '{optimizer}')")
+    if nesterov and not momentum > 0.0:
+        raise ValueError(f"--nesterov needs a momentum above 0 (got --momentum {momentum})")
 
 
 def add_args(p: argparse.ArgumentParser, mode_default: str = "sync") -> argparse.ArgumentParser:
@@ -74,6 +90,13 @@ def add_args(p: argparse.ArgumentParser, mode_default: str = "sync") -> argparse
     p.add_argument("--steps", type=int, default=None)
     p.add_argument("--lr", type=float, default=d.lr)
     p.add_argument("--optimizer", default=d.optimizer, choices=["adam", "momentum", "sgd"])
+    p.add_argument("--momentum", type=float, default=d.momentum,
+                   help="mu of --optimizer momentum")
+    p.add_argument("--weight-decay", type=float, default=d.weight_decay,
+                   help="decoupled weight decay (AdamW / SGDW): every parameter loses "
+                        "lr * wd of itself ahead of each update; 0 = off")
+    p.add_argument("--nesterov", action="store_true",
+                   help="Nesterov momentum (with --optimizer momentum and --momentum > 0)")
     p.add_argument("--keep-prob", type=float, default=d.keep_prob)
     p.add_argument("--eval-every", type=int, default=d.eval_every)
     p.add_argument("--data", default=d.data)
@@ -118,7 +141,8 @@ def from_args(a: argparse.Namespace) -> TrainConfig:
         mode, shard = VARIANTS[a.variant]["mode"], VARIANTS[a.variant]["shard"]
     return TrainConfig(
         mode=mode, shard=shard, num_ps=a.num_ps, epochs=a.epochs, batch_size=a.batch_size,
-        steps=a.steps, lr=a.lr, optimizer=a.optimizer, keep_prob=a.keep_prob,
+        steps=a.steps, lr=a.lr, optimizer=a.optimizer, momentum=a.momentum,
+        weight_decay=a.weight_decay, nesterov=a.nesterov, keep_prob=a.keep_prob,
         eval_every=a.eval_every, data=a.data, data_sharding=a.data_sharding,
         grad_reduce=a.grad_reduce, ref_quirks=a.ref_quirks, seed=a.seed, engine=a.engine,
         graph=a.graph and not a.no_graph, native_exchange=not a.no_native_exchange,

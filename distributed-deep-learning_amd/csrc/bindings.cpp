@@ -26,7 +26,8 @@ void check_f32_cuda(const at::Tensor& t, const char* name) {
 }
 
 // One update of a flat span under rule `kind` of update.h (copy: m and v may be None; momentum:
-// v may be).  The step size rides beside it: Adam's lr_t, or the learning rate.
+// v may be).  The step size rides beside it: Adam's lr_t, or the learning rate.  `decay` is the
+// decoupled weight decay's lr * wd, as a double: rounded to float here, once (update.h upd_decay).
 struct FlatUpdate {
   ddl::UpdRule rule;
   ddl::UpdSpan span;
@@ -34,9 +35,13 @@ struct FlatUpdate {
   int64_t n;
   FlatUpdate(int64_t kind, at::Tensor w, at::Tensor gt, c10::optional<at::Tensor> m,
              c10::optional<at::Tensor> v, double b1, double b2, double eps, double mu,
-             double scale)
-      : rule((int)kind, (float)b1, (float)b2, (float)eps, (float)mu, (float)scale), n(w.numel()) {
+             double scale, double decay = 0.0, bool nesterov = false)
+      : rule((int)kind, (float)b1, (float)b2, (float)eps, (float)mu, (float)scale, (float)decay,
+             nesterov),
+        n(w.numel()) {
     TORCH_CHECK(kind >= 0 && kind <= 2, "update: rule kind");
+    TORCH_CHECK(decay >= 0.0, "update: negative weight decay");
+    TORCH_CHECK(!nesterov || kind == ddl::kUpdMomentum, "update: Nesterov needs the momentum rule");
     TORCH_CHECK((m || kind == ddl::kUpdCopy) && (v || kind != ddl::kUpdAdam),
                 "update: optimizer state missing");
     auto ptr = [&](const at::Tensor& t, const char* name) {
@@ -53,16 +58,16 @@ struct FlatUpdate {
 
 void update_flat(int64_t kind, at::Tensor w, at::Tensor g, c10::optional<at::Tensor> m,
                  c10::optional<at::Tensor> v, double step, double b1, double b2, double eps,
-                 double mu, double scale) {
-  const FlatUpdate u(kind, w, g, m, v, b1, b2, eps, mu, scale);
+                 double mu, double scale, double decay, bool nesterov) {
+  const FlatUpdate u(kind, w, g, m, v, b1, b2, eps, mu, scale, decay, nesterov);
   ddl::launch_update(u.rule, (float)step, u.span, u.g, u.n, cur_stream());
 }
 void adam_flat(at::Tensor w, at::Tensor g, at::Tensor m, at::Tensor v, double lr_t, double b1,
                double b2, double eps, double scale) {
-  update_flat(ddl::kUpdAdam, w, g, m, v, lr_t, b1, b2, eps, 0.0, scale);
+  update_flat(ddl::kUpdAdam, w, g, m, v, lr_t, b1, b2, eps, 0.0, scale, 0.0, false);
 }
 void momentum_flat(at::Tensor w, at::Tensor g, at::Tensor m, double lr, double mu, double scale) {
-  update_flat(ddl::kUpdMomentum, w, g, m, c10::nullopt, lr, 0.0, 0.0, 0.0, mu, scale);
+  update_flat(ddl::kUpdMomentum, w, g, m, c10::nullopt, lr, 0.0, 0.0, 0.0, mu, scale, 0.0, false);
 }
 
 // Python-facing wrapper of ddl::Engine: owns the workspace tensor.
@@ -130,8 +135,8 @@ class PyEngine {
   // stand-alone launch (tests)
   void flush_update_tail(int64_t kind, at::Tensor w, at::Tensor g, c10::optional<at::Tensor> m,
                          c10::optional<at::Tensor> v, double step, double b1, double b2,
-                         double eps, double mu, double scale) {
-    const FlatUpdate u(kind, w, g, m, v, b1, b2, eps, mu, scale);
+                         double eps, double mu, double scale, double decay, bool nesterov) {
+    const FlatUpdate u(kind, w, g, m, v, b1, b2, eps, mu, scale, decay, nesterov);
     e_.flush_tail(cur_stream());
     ddl::UpdPiece q;
     q.w = u.span.w; q.g = u.g; q.m = u.span.m; q.v = u.span.v;
@@ -324,11 +329,13 @@ class PyPeer {
   // None where the rule, or a rank that does not own the bucket, has none.
   void launch(int64_t bucket, int64_t epoch, int64_t kind, c10::optional<at::Tensor> m,
               c10::optional<at::Tensor> v, double step, double b1, double b2, double eps,
-              double mu, double scale, double coef, bool final_wait) {
+              double mu, double scale, double coef, bool final_wait, double decay,
+              bool nesterov) {
     TORCH_CHECK(bucket >= 0 && bucket < p_->num_buckets(), "bucket out of range");
     TORCH_CHECK(kind >= 0 && kind <= 2, "update: rule kind");
     ddl::XgmiUpdate u;
-    u.rule = ddl::UpdRule((int)kind, (float)b1, (float)b2, (float)eps, (float)mu, (float)scale);
+    u.rule = ddl::UpdRule((int)kind, (float)b1, (float)b2, (float)eps, (float)mu, (float)scale,
+                          (float)decay, nesterov);
     u.step = (float)step;
     u.coef = (float)coef;
     auto state = [&](const at::Tensor& t, const char* name) {
@@ -410,10 +417,12 @@ class PyAsyncPeer {
   // (both step sizes stay in the Python-facing signature: parallel/async_xgmi.py is unchanged)
   void apply(int64_t ps, int64_t worker, int64_t epoch, int64_t opt, at::Tensor ps_params,
              c10::optional<at::Tensor> m, c10::optional<at::Tensor> v, double lr_t, double b1,
-             double b2, double eps, double lr, double mu, double scale) {
+             double b2, double eps, double lr, double mu, double scale, double weight_decay,
+             bool nesterov) {
     check_f32_cuda(ps_params, "ps_params");
     ddl::XgmiUpdate u;
-    u.rule = ddl::UpdRule((int)opt, (float)b1, (float)b2, (float)eps, (float)mu, (float)scale);
+    u.rule = ddl::UpdRule((int)opt, (float)b1, (float)b2, (float)eps, (float)mu, (float)scale,
+                          ddl::upd_decay(lr, weight_decay), nesterov);
     u.step = (float)(opt == ddl::kUpdMomentum ? lr : lr_t);
     if (m) { check_f32_cuda(*m, "m"); u.m = m->data_ptr<float>(); }
     if (v) { check_f32_cuda(*v, "v"); u.v = v->data_ptr<float>(); }
@@ -444,7 +453,7 @@ class PyAsyncService {
   // ps: list of (ps id, params, m, v | None, t)
   PyAsyncService(PyAsyncPeer& peer, int64_t world, py::list ps, int64_t opt,
                  double lr, double b1, double b2, double eps, double mu, double scale,
-                 int64_t epoch0, bool provenance) {
+                 int64_t epoch0, bool provenance, double weight_decay, bool nesterov) {
     std::vector<ddl::AsyncPsState> st;
     for (auto item : ps) {
       auto t = item.cast<py::tuple>();
@@ -470,7 +479,8 @@ class PyAsyncService {
     svc_ = std::make_unique<ddl::AsyncService>(peer.raw(), (int)world, peer.device(), st,
                                                (int)opt, (float)lr, (float)b1, (float)b2,
                                                (float)eps, (float)mu, (float)scale,
-                                               (uint32_t)epoch0, provenance);
+                                               (uint32_t)epoch0, provenance,
+                                               ddl::upd_decay(lr, weight_decay), nesterov);
   }
   void start(int64_t expected) { svc_->start(expected); }
   void join() {
@@ -498,7 +508,8 @@ class PyRcclAsync {
   // ps: list of (ps id, private params, m, v | None, t); ranges: [(lo, hi)] per PS
   PyRcclAsync(at::Tensor params, at::Tensor grads, int64_t world, int64_t rank, py::list ranges,
               std::vector<int64_t> hosts, py::list ps, int64_t opt, double lr, double b1,
-              double b2, double eps, double mu, bool self_sessions)
+              double b2, double eps, double mu, bool self_sessions, double weight_decay,
+              bool nesterov)
       : params_(params), grads_(grads) {
     check_f32_cuda(params, "params");
     check_f32_cuda(grads, "grads");
@@ -534,7 +545,8 @@ class PyRcclAsync {
     r_ = std::make_unique<ddl::RcclAsync>(params.data_ptr<float>(), grads.data_ptr<float>(),
                                           (int)world, (int)rank, params.device().index(), rg, h,
                                           st, (int)opt, lr, b1, b2, (float)eps, (float)mu,
-                                          self_sessions);
+                                          self_sessions, ddl::upd_decay(lr, weight_decay),
+                                          nesterov);
   }
   void init_comm(py::bytes id) {
     std::string s = id;
@@ -601,7 +613,7 @@ class PyAsyncRunner {
   void set_gate(bool on) { r_->set_gate(on); }
   // ps: list of (ps id, private params, m, v, t), every PS (W = 1, Adam)
   void set_inline(py::list ps, double lr, double b1, double b2, double eps, double scale,
-                  bool provenance) {
+                  bool provenance, double weight_decay) {
     std::vector<ddl::AsyncPsState> st;
     for (auto item : ps) {
       auto t = item.cast<py::tuple>();
@@ -622,7 +634,8 @@ class PyAsyncRunner {
       s.t = t[4].cast<int64_t>();
       st.push_back(s);
     }
-    r_->set_inline(st, (float)lr, (float)b1, (float)b2, (float)eps, (float)scale, provenance);
+    r_->set_inline(st, (float)lr, (float)b1, (float)b2, (float)eps, (float)scale, provenance,
+                   ddl::upd_decay(lr, weight_decay));
   }
   bool inline_on() const { return r_->inline_on(); }
   int64_t inline_t(int64_t ps) const { return r_->inline_t((int)ps); }
@@ -721,8 +734,13 @@ class PyRunner {
     }
     r_->set_units(out);
   }
-  void set_optimizer(int64_t kind, double lr, double b1, double b2, double eps, double mu) {
-    r_->set_optimizer((int)kind, (float)lr, (float)b1, (float)b2, (float)eps, (float)mu);
+  void set_optimizer(int64_t kind, double lr, double b1, double b2, double eps, double mu,
+                     double weight_decay, bool nesterov) {
+    TORCH_CHECK(weight_decay >= 0.0, "set_optimizer: negative weight decay");
+    TORCH_CHECK(!nesterov || kind == ddl::kUpdMomentum,
+                "set_optimizer: Nesterov needs the momentum rule");
+    r_->set_optimizer((int)kind, (float)lr, (float)b1, (float)b2, (float)eps, (float)mu,
+                      ddl::upd_decay(lr, weight_decay), nesterov);
   }
   void set_scale(double grad_scale, double coef) { r_->set_scale((float)grad_scale, (float)coef); }
   void set_local_on_main(bool on) { r_->set_local_on_main(on); }
@@ -778,7 +796,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("update_flat", &update_flat, "One update of a flat shard under rule `kind` (update.h)",
         py::arg("kind"), py::arg("w"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("step"),
         py::arg("b1") = 0.0, py::arg("b2") = 0.0, py::arg("eps") = 0.0, py::arg("mu") = 0.0,
-        py::arg("scale") = 1.0);
+        py::arg("scale") = 1.0, py::arg("decay") = 0.0, py::arg("nesterov") = false);
+  m.def("upd_decay", [](double lr, double weight_decay) {
+          return (double)ddl::upd_decay(lr, weight_decay);
+        }, "The decoupled weight decay's factor lr * wd as every rule carries it (float32, widened)");
   m.def("adam_step_size", [](double lr, double b1, double b2, int64_t t) {
           return (double)ddl::adam_step_size(lr, b1, b2, t);
         }, "TF1 Adam's lr_t at step t as the native runtime forms it (float32, returned widened)");
@@ -849,7 +870,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("get_eval_cfg", &PyEngine::get_eval_cfg)
       .def("set_concurrent", &PyEngine::set_concurrent)
       .def("set_dual", &PyEngine::set_dual)
-      .def("flush_update_tail", &PyEngine::flush_update_tail)
+      .def("flush_update_tail", &PyEngine::flush_update_tail, py::arg("kind"), py::arg("w"),
+           py::arg("g"), py::arg("m"), py::arg("v"), py::arg("step"), py::arg("b1"), py::arg("b2"),
+           py::arg("eps"), py::arg("mu"), py::arg("scale"), py::arg("decay") = 0.0,
+           py::arg("nesterov") = false)
       .def("set_conv1_direct", [](PyEngine& e, bool on) { e.raw()->conv1_direct = on; })
       .def("conv1_direct", [](PyEngine& e) { return e.raw()->conv1_direct; })
       .def("set_conv1_wgrad_direct", [](PyEngine& e, bool on) { e.raw()->conv1_wgrad_direct = on; })
@@ -879,7 +903,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("init_comm", &PyRunner::init_comm, py::arg("id"), py::arg("force") = false)
       .def("has_comm", &PyRunner::has_comm)
       .def("set_units", &PyRunner::set_units)
-      .def("set_optimizer", &PyRunner::set_optimizer)
+      .def("set_optimizer", &PyRunner::set_optimizer, py::arg("kind"), py::arg("lr"),
+           py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("mu"),
+           py::arg("weight_decay") = 0.0, py::arg("nesterov") = false)
       .def("set_scale", &PyRunner::set_scale)
       .def("set_local_on_main", &PyRunner::set_local_on_main)
       .def("set_last_on_main", &PyRunner::set_last_on_main)
@@ -907,15 +933,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("push_all", &PyAsyncPeer::push_all)
       .def("attach_done", &PyAsyncPeer::attach_done)
       .def("wait_done", &PyAsyncPeer::wait_done)
-      .def("apply", &PyAsyncPeer::apply)
+      .def("apply", &PyAsyncPeer::apply, py::arg("ps"), py::arg("worker"), py::arg("epoch"),
+           py::arg("opt"), py::arg("ps_params"), py::arg("m"), py::arg("v"), py::arg("lr_t"),
+           py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("lr"), py::arg("mu"),
+           py::arg("scale"), py::arg("weight_decay") = 0.0, py::arg("nesterov") = false)
       .def("unmap_peers", &PyAsyncPeer::unmap_peers)
       .def("close", &PyAsyncPeer::close)
       .def("error", &PyAsyncPeer::error);
 
   py::class_<PyAsyncService>(m, "AsyncService")
       .def(py::init<PyAsyncPeer&, int64_t, py::list, int64_t, double, double, double,
-                    double, double, double, int64_t, bool>(),
-           py::keep_alive<1, 2>())
+                    double, double, double, int64_t, bool, double, bool>(),
+           py::arg("peer"), py::arg("world"), py::arg("ps"), py::arg("opt"), py::arg("lr"),
+           py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("mu"), py::arg("scale"),
+           py::arg("epoch0"), py::arg("provenance"), py::arg("weight_decay") = 0.0,
+           py::arg("nesterov") = false, py::keep_alive<1, 2>())
       .def("start", &PyAsyncService::start)
       .def("join", &PyAsyncService::join)
       .def("t", &PyAsyncService::t)
@@ -927,7 +959,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
 
   py::class_<PyRcclAsync>(m, "RcclAsync")
       .def(py::init<at::Tensor, at::Tensor, int64_t, int64_t, py::list, std::vector<int64_t>,
-                    py::list, int64_t, double, double, double, double, double, bool>())
+                    py::list, int64_t, double, double, double, double, double, bool, double,
+                    bool>(),
+           py::arg("params"), py::arg("grads"), py::arg("world"), py::arg("rank"),
+           py::arg("ranges"), py::arg("hosts"), py::arg("ps"), py::arg("opt"), py::arg("lr"),
+           py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("mu"), py::arg("self_sessions"),
+           py::arg("weight_decay") = 0.0, py::arg("nesterov") = false)
       .def("init_comm", &PyRcclAsync::init_comm)
       .def("attach_shm", &PyRcclAsync::attach_shm)
       .def("open_boxes", &PyRcclAsync::open_boxes)
@@ -951,7 +988,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("epoch", &PyAsyncRunner::epoch)
       .def("set_use_tail", &PyAsyncRunner::set_use_tail)
       .def("set_gate", &PyAsyncRunner::set_gate)
-      .def("set_inline", &PyAsyncRunner::set_inline)
+      .def("set_inline", &PyAsyncRunner::set_inline, py::arg("ps"), py::arg("lr"), py::arg("b1"),
+           py::arg("b2"), py::arg("eps"), py::arg("scale"), py::arg("provenance"),
+           py::arg("weight_decay") = 0.0)
       .def("inline_on", &PyAsyncRunner::inline_on)
       .def("inline_t", &PyAsyncRunner::inline_t)
       .def("inline_sync_ps", &PyAsyncRunner::inline_sync_ps)
@@ -969,7 +1008,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("launch", &PyPeer::launch, py::arg("bucket"), py::arg("epoch"), py::arg("kind"),
            py::arg("m"), py::arg("v"), py::arg("step"), py::arg("b1"), py::arg("b2"),
            py::arg("eps"), py::arg("mu"), py::arg("scale"), py::arg("coef"),
-           py::arg("final_wait"))
+           py::arg("final_wait"), py::arg("decay") = 0.0, py::arg("nesterov") = false)
       .def("unmap_peers", &PyPeer::unmap_peers)
       .def("close", &PyPeer::close);
 

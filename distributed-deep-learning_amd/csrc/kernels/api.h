@@ -482,7 +482,7 @@ class AsyncService {
  public:
   AsyncService(AsyncPeer* peer, int world, int device, const std::vector<AsyncPsState>& ps,
                int opt, float lr, float b1, float b2, float eps, float mu, float scale,
-               uint32_t epoch0, bool provenance);
+               uint32_t epoch0, bool provenance, float decay = 0.f, bool nesterov = false);
   ~AsyncService();
   void start(int64_t expected);  // serve `expected` pushes on a native thread
   void join();                   // rethrows the thread's error, if any
@@ -543,7 +543,7 @@ class AsyncRunner {
   // equals the worker's buffer: inline_sync_ps() writes it back for checkpoints).  `ps` gives
   // every PS's m, v and t (its params pointer: the private copy).
   void set_inline(const std::vector<AsyncPsState>& ps, float lr, float b1, float b2, float eps,
-                  float scale, bool provenance);
+                  float scale, bool provenance, float decay = 0.f);
   bool inline_on() const { return inline_; }
   int64_t inline_t(int ps) const;
   void inline_sync_ps(hipStream_t st);  // worker buffer -> every PS's private copy
@@ -557,7 +557,7 @@ class AsyncRunner {
   UpdTail inline_tail(int seg, int f4_per_block);
   bool inline_ = false, keep_prov_ = false;
   std::vector<AsyncPsState> ips_;  // by PS id
-  UpdRule rule_;                   // Adam (the in-line applies have no other rule)
+  UpdRule rule_;                   // Adam or AdamW (the in-line applies have no other rule)
   float lr_ = 0.f, b1_ = 0.f, b2_ = 0.f;  // widened to double for adam_step_size (update.h)
   std::vector<float> lr_t_;        // this round's TF1 Adam step size per PS
   std::vector<std::array<int64_t, 4>> prov_;
@@ -583,7 +583,8 @@ class RcclAsync {
   RcclAsync(float* params, float* grads, int world, int rank, int device,
             const std::vector<std::pair<int64_t, int64_t>>& ps_ranges,
             const std::vector<int>& hosts, const std::vector<AsyncPsState>& hosted, int opt,
-            double lr, double b1, double b2, float eps, float mu, bool self_sessions);
+            double lr, double b1, double b2, float eps, float mu, bool self_sessions,
+            float decay = 0.f, bool nesterov = false);
   ~RcclAsync();
   void init_comm(const char id[128]);               // collective over all ranks
   void attach_shm(const std::string& job, bool create);  // session locks (rank 0 creates)
@@ -653,7 +654,10 @@ class SyncRunner {
   void init_comm(const char id[128], bool force = false);
   bool has_comm() const { return comm_ != nullptr; }
   void set_units(const std::vector<RunnerUnit>& units);
-  void set_optimizer(int kind, float lr, float b1, float b2, float eps, float mu);
+  // decay: update.h upd_decay(lr, weight decay).  A modified rule rides wherever its base rule
+  // does: the tail-path conditions test the kind only.
+  void set_optimizer(int kind, float lr, float b1, float b2, float eps, float mu,
+                     float decay = 0.f, bool nesterov = false);
   void set_scale(float grad_scale, float coef) { rule_.scale = grad_scale; coef_ = coef; }
   // one synchronous training step on stream `st`; lr_t indexed by RunnerUnit::ps
   void step(const float* x, const int64_t* labels, int B, uint32_t seed, const float* lr_t,

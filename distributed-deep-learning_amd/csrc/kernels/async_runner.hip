@@ -87,7 +87,7 @@ void AsyncRunner::check_round(uint32_t e, double timeout_s) {
 }
 
 void AsyncRunner::set_inline(const std::vector<AsyncPsState>& ps, float lr, float b1, float b2,
-                             float eps, float scale, bool provenance) {
+                             float eps, float scale, bool provenance, float decay) {
   const int P = peer_->num_ps();
   if (world_ != 1) throw std::invalid_argument("async runner: in-line applies need one worker");
   if ((int)ps.size() != P) throw std::invalid_argument("async runner: in-line applies need every PS");
@@ -106,7 +106,7 @@ void AsyncRunner::set_inline(const std::vector<AsyncPsState>& ps, float lr, floa
     by[s.ps] = s;
   }
   ips_ = by;
-  rule_ = UpdRule(kUpdAdam, b1, b2, eps, 0.f, scale);
+  rule_ = UpdRule(kUpdAdam, b1, b2, eps, 0.f, scale, decay);
   lr_ = lr;
   b1_ = b1;
   b2_ = b2;

@@ -107,6 +107,16 @@ DDL_DEV void momentum1(float& w, float g, float& m, float lr, float mu, float sc
   m = __fmaf_rn(m, mu, __fmul_rn(g, scale));
   w = __fmaf_rn(-lr, m, w);
 }
+// The same with Nesterov's look-ahead (tf.train.MomentumOptimizer(use_nesterov=True),
+// torch.optim.SGD(nesterov=True)): m as above, the step taken along mu * m + g * scale.
+DDL_DEV void nesterov1(float& w, float g, float& m, float lr, float mu, float scale) {
+  const float gs = __fmul_rn(g, scale);
+  m = __fmaf_rn(m, mu, gs);
+  w = __fmaf_rn(-lr, __fmaf_rn(mu, m, gs), w);
+}
+// Decoupled weight decay (AdamW / SGDW) of one element, ahead of the rule's own update:
+// w -= decay * w as one fma, decay = lr * wd (update.h upd_decay).
+DDL_DEV void decay1(float& w, float decay) { w = __fmaf_rn(-decay, w, w); }
 
 // Sum over aligned groups of RL lanes (RL = 1, 2, 4, ..., 64), returned in every lane of the
 // group.  DPP adds inside each 16-lane row (quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror,

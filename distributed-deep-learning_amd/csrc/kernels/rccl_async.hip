@@ -58,10 +58,11 @@ RcclAsync::RcclAsync(float* params, float* grads, int world, int rank, int devic
                      const std::vector<std::pair<int64_t, int64_t>>& ps_ranges,
                      const std::vector<int>& hosts, const std::vector<AsyncPsState>& hosted,
                      int opt, double lr, double b1, double b2, float eps, float mu,
-                     bool self_sessions)
+                     bool self_sessions, float decay, bool nesterov)
     : w_(params), g_(grads), world_(world), rank_(rank), device_(device), ranges_(ps_ranges),
       hosts_(hosts), ps_(hosted),
-      rule_(opt == 0 ? kUpdAdam : kUpdMomentum, (float)b1, (float)b2, eps, mu, 1.f),
+      rule_(opt == 0 ? kUpdAdam : kUpdMomentum, (float)b1, (float)b2, eps, mu, 1.f, decay,
+            nesterov),
       lr_((float)lr), lrd_(lr), b1d_(b1), b2d_(b2), self_(self_sessions) {
   if (world < 1 || world > kXgmiMaxPeers) throw std::invalid_argument("rccl async: world");
   if (ranges_.size() != hosts_.size() || ranges_.empty())

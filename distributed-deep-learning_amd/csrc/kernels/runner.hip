@@ -278,10 +278,11 @@ void SyncRunner::set_tail(int seg, const float* lr_t, int f4_per_block) {
   eng_->tail = t;
 }
 
-void SyncRunner::set_optimizer(int kind, float lr, float b1, float b2, float eps, float mu) {
+void SyncRunner::set_optimizer(int kind, float lr, float b1, float b2, float eps, float mu,
+                               float decay, bool nesterov) {
   if (kind != kUpdAdam && kind != kUpdMomentum)
     throw std::invalid_argument("native runner: adam or momentum");
-  rule_ = UpdRule(kind, b1, b2, eps, mu, rule_.scale);
+  rule_ = UpdRule(kind, b1, b2, eps, mu, rule_.scale, decay, nesterov);
   lr_ = lr;
 }
 

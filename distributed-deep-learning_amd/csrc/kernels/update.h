@@ -22,15 +22,30 @@ enum UpdKind : int {
   kUpdCopy = 2       // w := g, state untouched (the xGMI self-tests)
 };
 
+// UpdRule::flags
+enum UpdFlag : int {
+  kUpdNesterov = 1  // momentum: the step looks ahead, u = mu * m' + g * scale (else u = m')
+};
+
 struct UpdRule {
   int kind = kUpdAdam;
   float c1 = 0.f, c2 = 0.f, eps = 0.f;  // 1 - beta1, 1 - beta2, epsilon (Adam)
   float mu = 0.f;                       // momentum
   float scale = 1.f;                    // gradient scale (1/W mean, or 1 for the reference's sum)
+  // The two modifiers of a rule (kUpdCopy ignores both); the kind keeps its three values.
+  float decay = 0.f;  // decoupled weight decay lr * wd (upd_decay): w -= decay * w ahead of the
+                      // rule's own update, with the plain learning rate under Adam too; 0: none
+  int flags = 0;      // UpdFlag bits
   UpdRule() = default;
-  UpdRule(int kind_, float b1, float b2, float eps_, float mu_, float scale_)
-      : kind(kind_), c1(1.f - b1), c2(1.f - b2), eps(eps_), mu(mu_), scale(scale_) {}
+  UpdRule(int kind_, float b1, float b2, float eps_, float mu_, float scale_, float decay_ = 0.f,
+          bool nesterov = false)
+      : kind(kind_), c1(1.f - b1), c2(1.f - b2), eps(eps_), mu(mu_), scale(scale_),
+        decay(decay_), flags(nesterov ? kUpdNesterov : 0) {}
 };
+
+// The decay factor of a rule: lr * weight_decay formed in double and rounded once, so every site
+// that is given the same two doubles carries the same float.
+inline float upd_decay(double lr, double weight_decay) { return (float)(lr * weight_decay); }
 
 // Parameter and optimizer-state pointers of one range.  v is null under every rule but Adam and
 // is then neither offset nor touched.
@@ -54,13 +69,21 @@ inline float adam_step_size(double lr, double b1, double b2, int64_t t) {
 namespace ddl {
 
 // One element from the raw gradient g.  Both rules take g and the scale apart and pin their
-// roundings (common.h), so every site and kernel shape gives the same bits at every scale.
+// roundings (common.h), so every site and kernel shape gives the same bits at every scale; so do
+// the two modifiers (decoupled weight decay, Nesterov momentum).
 template <int KIND>
 DDL_DEV void upd1(const UpdRule& r, float step, float& w, float g, float& m, float& v) {
   static_assert(KIND == kUpdAdam || KIND == kUpdMomentum || KIND == kUpdCopy, "update rule");
-  if constexpr (KIND == kUpdAdam) adam1(w, g, r.scale, m, v, step, r.c1, r.c2, r.eps);
-  else if constexpr (KIND == kUpdMomentum) momentum1(w, g, m, step, r.mu, r.scale);
-  else w = g;
+  if constexpr (KIND == kUpdCopy) {
+    w = g;
+  } else {
+    // Both modifiers are wave-uniform tests of kernel-argument scalars.  The decay must be
+    // skipped, not run with a zero factor: fma(-0, w, w) turns w = -0.0 into +0.0.
+    if (r.decay != 0.f) decay1(w, r.decay);
+    if constexpr (KIND == kUpdAdam) adam1(w, g, r.scale, m, v, step, r.c1, r.c2, r.eps);
+    else if (r.flags & kUpdNesterov) nesterov1(w, g, m, step, r.mu, r.scale);
+    else momentum1(w, g, m, step, r.mu, r.scale);
+  }
 }
 template <int KIND>
 DDL_DEV void upd4(const UpdRule& r, float step, float4& w, const float4& g, float4& m,

@@ -642,9 +642,10 @@ int AsyncPeer::error() const { return err_ ? __atomic_load_n(err_, __ATOMIC_ACQU
 AsyncService::AsyncService(AsyncPeer* peer, int world, int device,
                            const std::vector<AsyncPsState>& ps, int opt, float lr, float b1,
                            float b2, float eps, float mu, float scale, uint32_t epoch0,
-                           bool provenance)
+                           bool provenance, float decay, bool nesterov)
     : peer_(peer), world_(world), device_(device), ps_(ps),
-      rule_(opt, b1, b2, eps, mu, scale), lr_(lr), b1_(b1), b2_(b2), keep_prov_(provenance) {
+      rule_(opt, b1, b2, eps, mu, scale, decay, nesterov), lr_(lr), b1_(b1), b2_(b2),
+      keep_prov_(provenance) {
   if (world < 1 || world > kXgmiMaxPeers) throw std::invalid_argument("async service: world");
   for (const auto& s : ps)
     if (s.ps < 0 || s.ps >= peer->num_ps() || !s.params || !s.m || (opt == 0 && !s.v))

@@ -57,12 +57,14 @@ class RcclAsyncExchange:
         mom = 0.0 if optimizer == "sgd" else (next(iter(servers.values())).momentum
                                               if servers else 0.9)
         hyper = h or _default_hyper()
+        ps0 = next(iter(servers.values())) if servers else None
+        wd, nesterov = (ps0.weight_decay, ps0.nesterov) if ps0 is not None else (0.0, False)
         ops = native.ops()
         ps_list = [(p, ps.params, ps.m, ps.v, ps.t) for p, ps in servers.items()]
         self.svc = ops.RcclAsync(params, grads, W, r, [tuple(map(int, x)) for x in self.ranges],
                                  [int(x) for x in self.hosts], ps_list,
                                  0 if optimizer == "adam" else 1, hyper.lr, hyper.beta1,
-                                 hyper.beta2, hyper.eps, mom, W == 1)
+                                 hyper.beta2, hyper.eps, mom, W == 1, wd, nesterov)
         # communicator: rank 0's unique id over the default group (every rank joins)
         ids = [None]
         if r == 0:

@@ -225,22 +225,23 @@ class AsyncPeerExchange:
         if n == 0:
             return
         ps_list = [(p, ps.params, ps.m, ps.v, ps.t) for p, ps in self.servers.items()]
-        h = next(iter(self.servers.values())).h
+        ps0 = next(iter(self.servers.values()))  # (every PS carries the run's hyper-parameters)
+        h = ps0.h
         if self.runner is not None and self.inline_ok and len(ps_list) == self.plan.num_ps and \
                 all(torch.equal(ps.params, self.params[lo:hi])
                     for p, ps in self.servers.items() for lo, hi in [self.ranges[p]]):
             # (a PS that does not start from the worker's parameters — --ref-quirks Q4 — keeps
             # the service: its apply stores the PS copy into the worker buffer)
             self.runner.set_inline(ps_list, h.lr, h.beta1, h.beta2, h.eps, self.grad_scale,
-                                   self.check_provenance)
+                                   self.check_provenance, ps0.weight_decay)
             self.inline = True
             self._inline_t0 = {p: ps.t for p, ps in self.servers.items()}
             self.service_mode = "inline"
             return
-        mom = next(iter(self.servers.values())).momentum if self.mu is None else self.mu
+        mom = ps0.momentum if self.mu is None else self.mu
         self._svc = native.ops().AsyncService(
             self.peer, self.env.world, ps_list, self.opt, h.lr, h.beta1, h.beta2, h.eps, mom,
-            self.grad_scale, 1, self.check_provenance)
+            self.grad_scale, 1, self.check_provenance, ps0.weight_decay, ps0.nesterov)
         self._svc.start(n)
         self.service_mode = self._svc.mode()  # "host": the native board-scan service
 

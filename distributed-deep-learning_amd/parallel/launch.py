@@ -21,7 +21,10 @@ def main(argv=None, mode_default: str = "sync") -> dict:
     ap = add_args(argparse.ArgumentParser(description=__doc__), mode_default)
     ap.add_argument("--summary-json", default=None)
     a = ap.parse_args(argv)
-    cfg = from_args(a)
+    try:
+        cfg = from_args(a)
+    except ValueError as e:  # (an option combination no update rule implements)
+        ap.error(str(e))
     from .comm import init_distributed
     from .roles import Trainer
     env = init_distributed()

@@ -80,7 +80,8 @@ class NativeSyncExchange(SyncExchange):
                  segments: Sequence[Sequence[int]], servers: Dict[int, ParameterServer], engine,
                  grad_reduce: str = "sum", ref_quirks: bool = False, overlap: bool = True,
                  optimizer: str = "adam", hyper=None, momentum: float = 0.9,
-                 force_collectives: bool = False, backend: str = "rccl"):
+                 force_collectives: bool = False, backend: str = "rccl",
+                 weight_decay: float = 0.0, nesterov: bool = False):
         if optimizer not in ("adam", "momentum", "sgd"):
             raise NativeUnavailable(f"native runner has no '{optimizer}' update")
         if optimizer == "sgd":
@@ -169,7 +170,7 @@ class NativeSyncExchange(SyncExchange):
         h = hyper if hyper is not None else next(iter(servers.values())).h
         # (before set_units: it checks each unit's optimizer state against the update kind)
         self.runner.set_optimizer(0 if optimizer == "adam" else 1, h.lr, h.beta1, h.beta2, h.eps,
-                                  momentum)
+                                  momentum, weight_decay, nesterov)
         self.runner.set_units(units)
         self.runner.set_scale(self.grad_scale, self.coef)
         # A/B knob: DDL_LAST_ON_MAIN=0 puts the last segment's collectives back on the comm
@@ -482,7 +483,8 @@ def make_sync_exchange(plan, env, params, grads, segments, servers, engine, cfg,
             return NativeSyncExchange(plan, env, params, grads, segments, servers, engine,
                                       cfg.grad_reduce, cfg.ref_quirks, cfg.overlap,
                                       cfg.optimizer, hyper, cfg.momentum,
-                                      force_collectives=cfg.force_collectives, backend=backend)
+                                      force_collectives=cfg.force_collectives, backend=backend,
+                                      weight_decay=cfg.weight_decay, nesterov=cfg.nesterov)
         except NativeUnavailable as e:
             if env.rank == 0 and getattr(engine, "name", "") == "hip":
                 print(f"[ddl_amd] native sync runner unavailable ({e}); using the Python "

@@ -22,18 +22,23 @@ import torch
 
 from .sharding import ShardPlan
 from ..ops import native
+from ..config import check_optimizer_options
 from ..ops.adam import AdamHyper, adam_coeffs
 
 
 class ParameterServer:
     def __init__(self, plan: ShardPlan, ps_id: int, device, hyper: Optional[AdamHyper] = None,
                  optimizer: str = "adam", momentum: float = 0.9,
-                 own_params: Optional[torch.Tensor] = None, native_optim: bool = True):
+                 own_params: Optional[torch.Tensor] = None, native_optim: bool = True,
+                 weight_decay: float = 0.0, nesterov: bool = False):
+        check_optimizer_options(optimizer, momentum, weight_decay, nesterov)
         self.plan, self.id, self.device = plan, ps_id, torch.device(device)
         # False only for the stock-PyTorch baseline engine (bench.py --engine torch)
         self.native_optim = native_optim
         self.h = hyper or AdamHyper()
         self.optimizer, self.momentum = optimizer, momentum
+        # decoupled weight decay (AdamW / SGDW) and Nesterov momentum: csrc/kernels/update.h
+        self.weight_decay, self.nesterov = weight_decay, nesterov
         self.segments: List[Tuple[int, int]] = plan.ps_segments(ps_id)
         self.seg_off: List[int] = []
         off = 0
@@ -88,10 +93,19 @@ class ParameterServer:
         at ``[state_off, state_off + w.numel())``."""
         n = w.numel()
         m = self.m[state_off:state_off + n]
+        use_native = w.is_cuda and self.native_optim
+        decay = self.h.lr * self.weight_decay  # (double; the kernels round it to float once)
+        if decay != 0.0 or self.nesterov:
+            if use_native:
+                self._apply_native_modified(w, g, m, state_off, grad_scale, decay)
+                return
+            if decay != 0.0:
+                # not bias-corrected: the plain learning rate under Adam too
+                w.sub_(w, alpha=decay)
         if self.optimizer == "adam":
             v = self.v[state_off:state_off + n]
             lr_t = adam_coeffs(self.h, self.t)
-            if w.is_cuda and self.native_optim:
+            if use_native:
                 native.ops().adam_flat(w, g, m, v, lr_t, self.h.beta1, self.h.beta2, self.h.eps,
                                        grad_scale)
             else:
@@ -105,13 +119,30 @@ class ParameterServer:
                 native.ops().momentum_flat(w, g, m, self.h.lr, self.momentum, grad_scale)
             else:
                 m.mul_(self.momentum).add_(g, alpha=grad_scale)
-                w.sub_(self.h.lr * m)
+                if self.nesterov:
+                    w.sub_(self.h.lr * (self.momentum * m + g * grad_scale))
+                else:
+                    w.sub_(self.h.lr * m)
         elif self.optimizer == "sgd":
             if w.is_cuda and self.native_optim:
                 # the fused momentum kernel with mu = 0: w -= lr * (g * scale)
                 native.ops().momentum_flat(w, g, m, self.h.lr, 0.0, grad_scale)
             else:
                 w.sub_(g * grad_scale if grad_scale != 1.0 else g, alpha=self.h.lr)
+        else:
+            raise ValueError(self.optimizer)
+
+    def _apply_native_modified(self, w, g, m, state_off, grad_scale, decay) -> None:
+        """The fused kernel with a modifier on (``update_flat`` of the extension)."""
+        h = self.h
+        if self.optimizer == "adam":
+            v = self.v[state_off:state_off + w.numel()]
+            native.ops().update_flat(0, w, g, m, v, adam_coeffs(h, self.t), h.beta1, h.beta2,
+                                     h.eps, 0.0, grad_scale, decay, False)
+        elif self.optimizer in ("momentum", "sgd"):
+            mu = self.momentum if self.optimizer == "momentum" else 0.0
+            native.ops().update_flat(1, w, g, m, None, h.lr, 0.0, 0.0, 0.0, mu, grad_scale, decay,
+                                     self.nesterov)
         else:
             raise ValueError(self.optimizer)
 

@@ -123,7 +123,9 @@ class Trainer:
                     own = tmp
             self.servers[p] = ParameterServer(self.plan, p, dev, hyper, cfg.optimizer,
                                               cfg.momentum, own_params=own,
-                                              native_optim=self.engine.name != "torch")
+                                              native_optim=self.engine.name != "torch",
+                                              weight_decay=cfg.weight_decay,
+                                              nesterov=cfg.nesterov)
         self.data = dataset if dataset is not None else get_dataset(cfg.data, seed=1234)
         self.data = self.data.to(dev)
         self.steps = cfg.steps or (self.data.total_batch // cfg.batch_size)

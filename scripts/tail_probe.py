@@ -7,8 +7,14 @@ every round visits every (optimizer, variant) pair in turn, so optimizers are co
 the same conditions as tail variants.  --variants default keeps the comparison to the tail
 off and the runner's default placement.
 
+--weight-decay WD and --nesterov add, beside every optimizer's plain trainer, one with the
+options on (adam+wd; momentum+nesterov+wd: Nesterov goes to the momentum trainers only), visited
+in the same rounds: the cost of the update rule's modifiers (csrc/kernels/update.h).
+
 usage: python scripts/tail_probe.py [--steps 300] [--rounds 3] [--optimizer momentum]
        python scripts/tail_probe.py --optimizer adam momentum sgd --variants default
+       python scripts/tail_probe.py --optimizer adam momentum --variants default \
+              --weight-decay 0.1 --nesterov
 """
 import argparse
 import os
@@ -28,6 +34,11 @@ def main():
     ap.add_argument("--variants", default="sweep", choices=["sweep", "default"],
                     help="sweep: off + both placements x 4 block sizes; default: off + the "
                          "runner's default tail")
+    ap.add_argument("--weight-decay", type=float, default=0.0,
+                    help="also time every optimizer with this decoupled weight decay")
+    ap.add_argument("--nesterov", action="store_true",
+                    help="also time momentum with Nesterov's look-ahead (with --weight-decay: "
+                         "both on one trainer)")
     a = ap.parse_args()
     import torch
     from ddl_amd.config import TrainConfig
@@ -39,9 +50,18 @@ def main():
     data = synthetic_mnist()
     trainers = {}
     for opt in dict.fromkeys(a.optimizer):
-        cfg = TrainConfig(mode="sync", shard=a.shard, steps=10 ** 6, batch_size=100, eval_every=0,
-                          engine="hip", quiet=True, data_sharding="stride", optimizer=opt)
-        trainers[opt] = Trainer(cfg, env, dataset=data)
+        mods = [{}]
+        on = dict(weight_decay=a.weight_decay) if a.weight_decay else {}
+        if a.nesterov and opt == "momentum":
+            on["nesterov"] = True
+        if on:
+            mods.append(on)
+        for kw in mods:
+            cfg = TrainConfig(mode="sync", shard=a.shard, steps=10 ** 6, batch_size=100,
+                              eval_every=0, engine="hip", quiet=True, data_sharding="stride",
+                              optimizer=opt, **kw)
+            name = opt + ("+nesterov" if kw.get("nesterov") else "") + ("+wd" if "weight_decay" in kw else "")
+            trainers[name] = Trainer(cfg, env, dataset=data)
     if a.variants == "default":
         variants = [("off", None), ("tail", ())]
     else:
@@ -72,7 +92,7 @@ def main():
                 res[opt, name].append(1e6 * (time.perf_counter() - t0) / a.steps)
                 launches[opt, name] = run.update_launches()
     for (opt, name), ts in res.items():
-        print(f"{opt:9s}{name:16s} us/step min {min(ts):7.1f}  spread {max(ts) - min(ts):5.1f}  "
+        print(f"{opt:21s}{name:16s} us/step min {min(ts):7.1f}  spread {max(ts) - min(ts):5.1f}  "
               f"all {' '.join(f'{t:.1f}' for t in ts)}  update launches/step "
               f"{launches[opt, name]}")
 
