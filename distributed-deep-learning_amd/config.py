@@ -28,6 +28,7 @@ class TrainConfig:
     momentum: float = 0.9
     weight_decay: float = 0.0       # decoupled (AdamW / SGDW): w -= lr * wd * w before each update
     nesterov: bool = False          # momentum only: step along mu * m' + g
+    clip_norm: float = 0.0          # clip each worker's gradient to this global norm; 0 = off
     keep_prob: float = 0.5
     eval_every: int = 10            # 0 disables periodic eval
     data: str = "synthetic"
@@ -58,6 +59,7 @@ class TrainConfig:
 
     def __post_init__(self):
         check_optimizer_options(self.optimizer, self.momentum, self.weight_decay, self.nesterov)
+        check_clip_norm(self.clip_norm)
 
     def to_dict(self):
         return asdict(self)
@@ -72,6 +74,12 @@ def check_optimizer_options(optimizer: str, momentum: float, weight_decay: float
         raise ValueError(f"--nesterov needs --optimizer momentum (got '{optimizer}')")
     if nesterov and not momentum > 0.0:
         raise ValueError(f"--nesterov needs a momentum above 0 (got --momentum {momentum})")
+
+
+def check_clip_norm(clip_norm: float) -> None:
+    """Refuse a clip norm that is negative (or not a number); 0 switches clipping off."""
+    if not clip_norm >= 0.0:
+        raise ValueError(f"--clip-norm must not be negative (got {clip_norm})")
 
 
 def add_args(p: argparse.ArgumentParser, mode_default: str = "sync") -> argparse.ArgumentParser:
@@ -97,6 +105,10 @@ def add_args(p: argparse.ArgumentParser, mode_default: str = "sync") -> argparse
                         "lr * wd of itself ahead of each update; 0 = off")
     p.add_argument("--nesterov", action="store_true",
                    help="Nesterov momentum (with --optimizer momentum and --momentum > 0)")
+    p.add_argument("--clip-norm", type=float, default=d.clip_norm,
+                   help="clip each worker's mini-batch gradient to this global norm before it is "
+                        "scaled, pushed, reduced or applied (tf.clip_by_global_norm on the "
+                        "worker); the step then runs without backward/exchange overlap; 0 = off")
     p.add_argument("--keep-prob", type=float, default=d.keep_prob)
     p.add_argument("--eval-every", type=int, default=d.eval_every)
     p.add_argument("--data", default=d.data)
@@ -142,7 +154,8 @@ def from_args(a: argparse.Namespace) -> TrainConfig:
     return TrainConfig(
         mode=mode, shard=shard, num_ps=a.num_ps, epochs=a.epochs, batch_size=a.batch_size,
         steps=a.steps, lr=a.lr, optimizer=a.optimizer, momentum=a.momentum,
-        weight_decay=a.weight_decay, nesterov=a.nesterov, keep_prob=a.keep_prob,
+        weight_decay=a.weight_decay, nesterov=a.nesterov, clip_norm=a.clip_norm,
+        keep_prob=a.keep_prob,
         eval_every=a.eval_every, data=a.data, data_sharding=a.data_sharding,
         grad_reduce=a.grad_reduce, ref_quirks=a.ref_quirks, seed=a.seed, engine=a.engine,
         graph=a.graph and not a.no_graph, native_exchange=not a.no_native_exchange,

@@ -70,6 +70,56 @@ void momentum_flat(at::Tensor w, at::Tensor g, at::Tensor m, double lr, double m
   update_flat(ddl::kUpdMomentum, w, g, m, c10::nullopt, lr, 0.0, 0.0, 0.0, mu, scale, 0.0, false);
 }
 
+// Clip by global norm (kernels/clip.hip).  ranges: [(lo, n)] element ranges of grads, at most 16.
+ddl::ClipRanges clip_table(const at::Tensor& grads, const std::vector<std::pair<int64_t, int64_t>>& ranges) {
+  check_f32_cuda(grads, "grads");
+  return ddl::make_clip_ranges(ranges, std::max<int64_t>(grads.numel(), 1));
+}
+// A runner's clipping site: the table plus scratch tensors it keeps alive (out: 2 floats)
+struct PyClipSite {
+  ddl::ClipSite site;
+  std::vector<at::Tensor> keep;
+  void set(double max_norm, const at::Tensor& grads,
+           const std::vector<std::pair<int64_t, int64_t>>& ranges, at::Tensor out) {
+    TORCH_CHECK(max_norm >= 0.0, "set_clip: negative max_norm");
+    site = ddl::ClipSite();
+    keep.clear();
+    if (max_norm == 0.0) return;
+    check_f32_cuda(out, "out");
+    TORCH_CHECK(out.numel() >= 2, "set_clip: out holds {norm, coef}");
+    site.ranges = clip_table(grads, ranges);
+    site.max_norm = (float)max_norm;
+    TORCH_CHECK(site.max_norm > 0.f, "set_clip: max_norm rounds to 0 in float32");
+    at::Tensor part = at::empty({std::max(site.ranges.nchunks, 1)}, grads.options().dtype(at::kDouble));
+    at::Tensor ticket = at::zeros({1}, grads.options().dtype(at::kInt));
+    site.out2 = out.data_ptr<float>();
+    site.partials = part.data_ptr<double>();
+    site.ticket = ticket.data_ptr<int>();
+    keep = {out, part, ticket};
+  }
+};
+
+// Stand-alone: out <- {norm, coef}, grads scaled in place (no host sync).  The arrival ticket is
+// one zeroed word per device, left zero by every call: calls on one device must be ordered (one
+// stream at a time).
+void clip_grads(at::Tensor grads, std::vector<std::pair<int64_t, int64_t>> ranges, double max_norm,
+                at::Tensor out, int64_t max_grid) {
+  TORCH_CHECK(max_norm > 0.0 && (float)max_norm > 0.f, "clip_grads: max_norm must be positive");
+  check_f32_cuda(out, "out");
+  TORCH_CHECK(out.numel() >= 2, "clip_grads: out holds {norm, coef}");
+  const ddl::ClipRanges t = clip_table(grads, ranges);
+  c10::hip::HIPGuard guard(grads.device().index());
+  // (never destroyed: a device tensor must not outlive into static destruction)
+  static std::vector<at::Tensor>& tickets = *new std::vector<at::Tensor>(64);
+  const int dev = grads.device().index();
+  TORCH_CHECK(dev >= 0 && dev < 64, "clip_grads: device index");
+  if (!tickets[dev].defined()) tickets[dev] = at::zeros({1}, grads.options().dtype(at::kInt));
+  at::Tensor part = at::empty({std::max(t.nchunks, 1)}, grads.options().dtype(at::kDouble));
+  ddl::launch_clip(t, grads.data_ptr<float>(), (float)max_norm, out.data_ptr<float>(),
+                   part.data_ptr<double>(), tickets[dev].data_ptr<int>(), cur_stream(),
+                   (int)max_grid);
+}
+
 // Python-facing wrapper of ddl::Engine: owns the workspace tensor.
 class PyEngine {
  public:
@@ -441,6 +491,7 @@ class PyAsyncPeer {
   int error() const { return p_->error(); }
   ddl::AsyncPeer* raw() { return p_.get(); }
   int device() const { return params_.device().index(); }
+  const at::Tensor& grads() const { return grads_; }
 
  private:
   at::Tensor params_, grads_;
@@ -587,7 +638,7 @@ class PyAsyncRunner {
  public:
   PyAsyncRunner(PyEngine& eng, PyAsyncPeer& peer, int64_t world, int64_t rank,
                 std::vector<int64_t> seg_of_ps, int64_t epoch0)
-      : eng_(eng) {
+      : eng_(eng), grads_(peer.grads()) {
     std::vector<int> seg(seg_of_ps.begin(), seg_of_ps.end());
     c10::hip::HIPGuard guard(peer.device());
     r_ = std::make_unique<ddl::AsyncRunner>(eng.raw(), peer.raw(), (int)world, (int)rank,
@@ -611,6 +662,11 @@ class PyAsyncRunner {
   int64_t epoch() const { return r_->epoch(); }
   void set_use_tail(bool on) { r_->set_use_tail(on); }
   void set_gate(bool on) { r_->set_gate(on); }
+  // clip every round's gradient by its global norm before it is pushed / applied (max_norm 0: off)
+  void set_clip(double max_norm, std::vector<std::pair<int64_t, int64_t>> ranges, at::Tensor out) {
+    clip_.set(max_norm, grads_, ranges, out);
+    r_->set_clip(clip_.site);
+  }
   // ps: list of (ps id, private params, m, v, t), every PS (W = 1, Adam)
   void set_inline(py::list ps, double lr, double b1, double b2, double eps, double scale,
                   bool provenance, double weight_decay) {
@@ -644,6 +700,8 @@ class PyAsyncRunner {
 
  private:
   PyEngine& eng_;
+  at::Tensor grads_;
+  PyClipSite clip_;
   std::vector<at::Tensor> keep_;
   std::unique_ptr<ddl::AsyncRunner> r_;
 };
@@ -743,6 +801,11 @@ class PyRunner {
                       ddl::upd_decay(lr, weight_decay), nesterov);
   }
   void set_scale(double grad_scale, double coef) { r_->set_scale((float)grad_scale, (float)coef); }
+  // clip the step's gradient by its global norm; out: {norm, coef} after each step (max_norm 0: off)
+  void set_clip(double max_norm, std::vector<std::pair<int64_t, int64_t>> ranges, at::Tensor out) {
+    clip_.set(max_norm, grads_, ranges, out);
+    r_->set_clip(clip_.site);
+  }
   void set_local_on_main(bool on) { r_->set_local_on_main(on); }
   void set_last_on_main(bool on) { r_->set_last_on_main(on); }
   void set_ready_flags(int64_t mode) { r_->set_ready_flags((int)mode); }
@@ -780,6 +843,7 @@ class PyRunner {
   at::Tensor params_, grads_;
   std::vector<at::Tensor> keep_;
   std::vector<float> lr_;
+  PyClipSite clip_;
   std::unique_ptr<ddl::SyncRunner> r_;
   int64_t world_;
   PyPeer* peer_keep_ = nullptr;
@@ -797,6 +861,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("kind"), py::arg("w"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("step"),
         py::arg("b1") = 0.0, py::arg("b2") = 0.0, py::arg("eps") = 0.0, py::arg("mu") = 0.0,
         py::arg("scale") = 1.0, py::arg("decay") = 0.0, py::arg("nesterov") = false);
+  m.def("clip_grads", &clip_grads,
+        "Clip grads in place by the global norm over `ranges` [(lo, n)]; out <- {norm, coef}",
+        py::arg("grads"), py::arg("ranges"), py::arg("max_norm"), py::arg("out"),
+        py::arg("max_grid") = 0);
+  m.attr("CLIP_CHUNK") = (int)ddl::kClipChunk;
+  m.attr("CLIP_SLOTS") = (int)ddl::kClipSlots;
   m.def("upd_decay", [](double lr, double weight_decay) {
           return (double)ddl::upd_decay(lr, weight_decay);
         }, "The decoupled weight decay's factor lr * wd as every rule carries it (float32, widened)");
@@ -907,6 +977,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("mu"),
            py::arg("weight_decay") = 0.0, py::arg("nesterov") = false)
       .def("set_scale", &PyRunner::set_scale)
+      .def("set_clip", &PyRunner::set_clip, py::arg("max_norm"), py::arg("ranges"), py::arg("out"))
       .def("set_local_on_main", &PyRunner::set_local_on_main)
       .def("set_last_on_main", &PyRunner::set_last_on_main)
       .def("set_use_tail", &PyRunner::set_use_tail)
@@ -988,6 +1059,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("epoch", &PyAsyncRunner::epoch)
       .def("set_use_tail", &PyAsyncRunner::set_use_tail)
       .def("set_gate", &PyAsyncRunner::set_gate)
+      .def("set_clip", &PyAsyncRunner::set_clip, py::arg("max_norm"), py::arg("ranges"),
+           py::arg("out"))
       .def("set_inline", &PyAsyncRunner::set_inline, py::arg("ps"), py::arg("lr"), py::arg("b1"),
            py::arg("b2"), py::arg("eps"), py::arg("scale"), py::arg("provenance"),
            py::arg("weight_decay") = 0.0)

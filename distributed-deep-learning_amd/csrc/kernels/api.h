@@ -17,6 +17,7 @@
 #include <thread>
 #include <vector>
 
+#include "clip_ranges.h"
 #include "runtime/session.h"
 #include "scratch.h"
 #include "tail.h"
@@ -32,6 +33,26 @@ class ShmMailbox;
 void launch_update(const UpdRule& r, float step, const UpdSpan& s, const float* g, int64_t n,
                    hipStream_t st, int max_grid = 2048);
 void launch_scale(float* p, int64_t n, float a, hipStream_t st);
+
+// ---- clip by global norm (clip.hip) ----------------------------------------------------------
+// norm over the ranges of g (clip_ranges.h), coef = max_norm / norm when norm > max_norm else 1
+// (also when the norm is not finite), g *= coef in place unless coef == 1.  out2: {norm, coef}
+// on the device; partials: t.nchunks doubles; ticket: one zeroed int (left zero).  Two launches,
+// no host sync; the bits depend on (contents, ranges, max_norm) only, not on max_grid.
+void launch_clip(const ClipRanges& t, float* g, float max_norm, float* out2, double* partials,
+                 int* ticket, hipStream_t st, int max_grid = 0);
+// one clipping site of a step runner (set_clip): the table and the caller's device scratch
+struct ClipSite {
+  ClipRanges ranges;
+  float max_norm = 0.f;          // 0: off
+  float* out2 = nullptr;
+  double* partials = nullptr;
+  int* ticket = nullptr;
+  bool on() const { return max_norm > 0.f; }
+  void launch(float* g, hipStream_t st) const {
+    launch_clip(ranges, g, max_norm, out2, partials, ticket, st);
+  }
+};
 
 // ---- conv1 forward as a direct LDS-staged kernel (conv1.hip) --------------------------------
 // x [B,784], w [25,32], bias [32] -> pooled p1 [B,18,18,32] (halo layout) + codes [B,14,14,32]
@@ -535,6 +556,10 @@ class AsyncRunner {
   void set_use_tail(bool on) { use_tail_ = on; }
   // the pull as a GPU-side gate before the next forward (default) or a host wait
   void set_gate(bool on) { gate_ = on; }
+  // clip this worker's gradient by its global norm (clip.hip) before any push or in-line apply:
+  // the whole backward runs first, with no tails, then the clip, then the pushes / applies in
+  // segment order.  max_norm 0: off
+  void set_clip(const ClipSite& c) { clip_ = c; }
   // In-line applies (one worker, every PS hosted by it, Adam): each push is applied on the
   // compute stream as Adam tail blocks of the next segment's launch — the last segment's inside
   // conv1's weight-gradient launch — with the PS's m / v and its own step counter t, in push
@@ -565,6 +590,7 @@ class AsyncRunner {
   bool stepped_ = false;
   bool use_tail_ = true;
   bool gate_ = true;
+  ClipSite clip_;
   uint32_t gated_ = 0;  // the round the last step's gate waits for (0: none)
   hipStream_t safe_stream_ = nullptr;  // the compute stream whose priority was checked
   bool safe_checked_ = false, safe_ = false;
@@ -659,6 +685,10 @@ class SyncRunner {
   void set_optimizer(int kind, float lr, float b1, float b2, float eps, float mu,
                      float decay = 0.f, bool nesterov = false);
   void set_scale(float grad_scale, float coef) { rule_.scale = grad_scale; coef_ = coef; }
+  // clip this worker's gradient by its global norm (clip.hip) after the fourth backward segment
+  // and before anything consumes it.  The caller maps every unit to the last segment; the tail
+  // and final-in-reduce placements are not taken, as with coef_ != 1.  max_norm 0: off
+  void set_clip(const ClipSite& c) { clip_ = c; }
   // one synchronous training step on stream `st`; lr_t indexed by RunnerUnit::ps
   void step(const float* x, const int64_t* labels, int B, uint32_t seed, const float* lr_t,
             hipStream_t st);
@@ -733,6 +763,7 @@ class SyncRunner {
   UpdRule rule_{kUpdAdam, 0.9f, 0.999f, 1e-8f, 0.9f, 1.f};  // (scale: set_scale's grad_scale)
   float lr_ = 1e-4f;       // momentum's step size (Adam's lr_t comes with every step())
   float coef_ = 1.f;
+  ClipSite clip_;
   // a range's parameter / optimizer-state span (state at state_off of the owning PS's m / v)
   UpdSpan span_of(const RunnerRange& r, float* m, float* v) const {
     return UpdSpan{w_ + r.lo, m + r.state_off, v ? v + r.state_off : nullptr};

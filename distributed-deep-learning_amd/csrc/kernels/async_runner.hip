@@ -180,6 +180,18 @@ void AsyncRunner::step_inline(const float* x, const int64_t* labels, int B, hipS
                     peer_->grads() + lo, n, st);
     }
   };
+  if (clip_.on()) {
+    // the norm needs the whole backward: no tails; clip, then every segment's applies in
+    // segment order (the push order of the unclipped step)
+    for (int s = 0; s < kSegments; ++s) {
+      TraceRange r("ddl.bwd");
+      eng_->backward_segment(s, x, labels, B, nullptr, st);
+      eng_->flush_tail(st);
+    }
+    clip_.launch(const_cast<float*>(peer_->grads()), st);
+    for (int s = 0; s < kSegments; ++s) apply_now(s);
+    return;
+  }
   for (int s = 0; s < kSegments; ++s) {
     TraceRange r("ddl.bwd");
     if (s > 0 && !seg_ps_[s - 1].empty()) {
@@ -241,8 +253,19 @@ void AsyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t se
   int last = kSegments - 1;
   while (last > 0 && seg_ps_[last].empty()) --last;
   gated_ = 0;
+  const bool clip = clip_.on();
+  if (clip) {
+    // a clipped round: the whole backward with no push tails, the clip, then the pushes below
+    // in segment order (push kernels of their own; the last carries the gate)
+    for (int s = 0; s < kSegments; ++s) {
+      TraceRange r("ddl.bwd");
+      eng_->backward_segment(s, x, labels, B, nullptr, st);
+    }
+    eng_->flush_tail(st);
+    clip_.launch(const_cast<float*>(peer_->grads()), st);
+  }
   for (int s = 0; s < kSegments; ++s) {
-    {
+    if (!clip) {
       TraceRange r("ddl.bwd");
       eng_->backward_segment(s, x, labels, B, nullptr, st);  // (takes a pending push tail)
     }
@@ -252,7 +275,7 @@ void AsyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t se
     // segment's by a push kernel
     TraceRange r("ddl.async.worker.push");
     UpdTail t;
-    if (use_tail_ && s + 1 < kSegments && peer_->push_tail(seg_ps_[s], epoch_, t)) {
+    if (!clip && use_tail_ && s + 1 < kSegments && peer_->push_tail(seg_ps_[s], epoch_, t)) {
       eng_->flush_tail(st);
       eng_->tail = t;
     } else {

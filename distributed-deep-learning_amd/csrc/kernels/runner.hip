@@ -384,6 +384,10 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
   if (closed_) throw std::runtime_error("sync runner: step() after close()");
   TraceRange step_range("ddl.step");
   upd_launches_ = eng_->update_launches = 0;  // (host counters: update_launches())
+  if (clip_.on())
+    for (const auto& u : units_)
+      if (u.seg != kSegments - 1)
+        throw std::invalid_argument("sync runner: a clipped step needs every unit on the last segment");
   eng_->seed_value = seed_value;  // dropout seed by kernel argument: no seed-upload kernel
   const uint32_t* seed = nullptr;
   // Cross-queue dependencies (event record -> stream wait) cost tens of microseconds of GPU
@@ -397,7 +401,7 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
   // (Adam needs every piece's v; momentum / SGD have none and form none)
   if (all_local_ && local_on_main_ && use_tail_ && tail_ok_ &&
       (rule_.kind == kUpdMomentum || tail_v_ok_) &&
-      coef_ == 1.f) {
+      coef_ == 1.f && !clip_.on()) {
     // segment s-1's update rides in segment s's dual launch (flushed as a launch of its own
     // if the segment had no dual launch to take it); the last segment's follows the backward
     for (int s = 0; s < kSegments; ++s) {
@@ -429,6 +433,7 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
       TraceRange r(kBwdRange[s]);
       eng_->backward_segment(s, x, labels, B, seed, st);
     }
+    if (clip_.on()) clip_.launch(g_, st);
     TraceRange r("ddl.update");
     if (coef_ != 1.f)
       for (const auto& p : merged_) scale_grads(g_ + p.r.lo, p.r.hi - p.r.lo, st);
@@ -464,7 +469,9 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
     // otherwise the comm stream waits for this segment's gradients by an event: bound to the
     // segment's kernel launches themselves (the wait below is issued after the last one) rather
     // than a marker packet behind them
-    const bool bind = ext_event_ && !on_main && seg_offstream_[s] && !flag;
+    // (a clipped step's gradients are complete only after the clip, which follows the segment's
+    // launches: a marker record behind it, not an event bound to the segment's last launch)
+    const bool bind = ext_event_ && !on_main && seg_offstream_[s] && !flag && !clip_.on();
     // bound to the segment's LAST launch (its count is learned from the previous step; a
     // wrong or unknown count falls back to a marker record below, which supersedes the binding)
     bool marker = !bind;
@@ -479,6 +486,9 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
         seg_launches_[s] = n;
       }
     }
+    // every unit is the last segment's (checked above): the worker's own clipped gradient is
+    // what every exchange and update below reads
+    if (clip_.on() && s == kSegments - 1) clip_.launch(g_, st);
     TraceRange ex_range(kExRange[s]);
     hipStream_t xs = on_main ? st : cs_;
     bool waited = on_main;

@@ -81,7 +81,7 @@ class NativeSyncExchange(SyncExchange):
                  grad_reduce: str = "sum", ref_quirks: bool = False, overlap: bool = True,
                  optimizer: str = "adam", hyper=None, momentum: float = 0.9,
                  force_collectives: bool = False, backend: str = "rccl",
-                 weight_decay: float = 0.0, nesterov: bool = False):
+                 weight_decay: float = 0.0, nesterov: bool = False, clip=None):
         if optimizer not in ("adam", "momentum", "sgd"):
             raise NativeUnavailable(f"native runner has no '{optimizer}' update")
         if optimizer == "sgd":
@@ -173,6 +173,13 @@ class NativeSyncExchange(SyncExchange):
                                   momentum, weight_decay, nesterov)
         self.runner.set_units(units)
         self.runner.set_scale(self.grad_scale, self.coef)
+        # clip = (max_norm, [(lo, n)] payload ranges, the {norm, coef} buffer): the runner clips
+        # after the fourth backward segment (the caller passed overlap=False: every unit above
+        # is the last segment's)
+        if clip is not None:
+            if overlap:
+                raise ValueError("a clipped step has no per-segment hand-off: overlap=False")
+            self.runner.set_clip(*clip)
         # A/B knob: DDL_LAST_ON_MAIN=0 puts the last segment's collectives back on the comm
         # stream (one event hop more on the critical path of every W > 1 step)
         self.runner.set_last_on_main(os.environ.get("DDL_LAST_ON_MAIN", "1") != "0")
@@ -474,20 +481,26 @@ def handoff_vote(env, digest_events: str, digest_flags: str) -> dict:
             "ranks_agree": ranks_agree}
 
 
-def make_sync_exchange(plan, env, params, grads, segments, servers, engine, cfg, hyper):
+def make_sync_exchange(plan, env, params, grads, segments, servers, engine, cfg, hyper,
+                       clip=None):
     """Native runner when it applies (HIP engine, sync, adam/momentum/sgd), else the Python
-    exchange.  On a multi-GPU job the choice is collective (self-test votes)."""
+    exchange.  On a multi-GPU job the choice is collective (self-test votes).  clip: the
+    trainer's (max_norm, ranges, out) when --clip-norm is on; the native runner then clips
+    itself, the Python exchange's caller clips between the backward and finish_step().  Either
+    way nothing is handed over per segment (overlap off)."""
+    overlap = cfg.overlap and clip is None
     if cfg.native_exchange:
         try:
             backend = cfg.exchange_backend if cfg.exchange_backend != "auto" else "rccl"
             return NativeSyncExchange(plan, env, params, grads, segments, servers, engine,
-                                      cfg.grad_reduce, cfg.ref_quirks, cfg.overlap,
+                                      cfg.grad_reduce, cfg.ref_quirks, overlap,
                                       cfg.optimizer, hyper, cfg.momentum,
                                       force_collectives=cfg.force_collectives, backend=backend,
-                                      weight_decay=cfg.weight_decay, nesterov=cfg.nesterov)
+                                      weight_decay=cfg.weight_decay, nesterov=cfg.nesterov,
+                                      clip=clip)
         except NativeUnavailable as e:
             if env.rank == 0 and getattr(engine, "name", "") == "hip":
                 print(f"[ddl_amd] native sync runner unavailable ({e}); using the Python "
                       f"exchange", file=sys.stderr)
     return SyncExchange(plan, env, params, grads, segments, servers, cfg.grad_reduce,
-                        cfg.ref_quirks, overlap=cfg.overlap)
+                        cfg.ref_quirks, overlap=overlap)

@@ -26,6 +26,7 @@ from ..config import TrainConfig
 from ..models import make_engine, engine_segments
 from ..models.mnist_cnn import init_params_
 from ..ops import rng
+from ..ops import clip as clip_ops
 from ..ops.adam import AdamHyper
 from ..utils import metrics
 from ..utils.data import Dataset, get_dataset, batch_indices
@@ -129,13 +130,22 @@ class Trainer:
         self.data = dataset if dataset is not None else get_dataset(cfg.data, seed=1234)
         self.data = self.data.to(dev)
         self.steps = cfg.steps or (self.data.total_batch // cfg.batch_size)
+        # Clipping by the global norm (ops/clip.py, csrc/kernels/clip.hip): the worker's own
+        # gradient, before anything else reads it.  The norm needs the whole backward, so a
+        # clipped step hands nothing over per segment: every exchange unit is the last segment's.
+        self.clip_ranges = clip_ops.payload_ranges(self.plan.tensor_offsets)
+        self.clip_out = (torch.zeros(2, dtype=torch.float32, device=dev)  # {norm, coef}
+                         if cfg.clip_norm > 0 else None)
+        clip = (cfg.clip_norm, self.clip_ranges, self.clip_out) if cfg.clip_norm > 0 else None
         if asyncm and not self.async_as_sync:
             self.exchange = self._make_async_exchange(cfg, env)
             if hasattr(self.exchange, "attach_runner"):
                 self.exchange.attach_runner(self.engine, segs)
+                if clip is not None and self.exchange.runner is not None:
+                    self.exchange.runner.set_clip(*clip)
         else:
             self.exchange = make_sync_exchange(self.plan, env, self.params, self.grads, segs,
-                                               self.servers, self.engine, cfg, hyper)
+                                               self.servers, self.engine, cfg, hyper, clip=clip)
         self.log = metrics.JsonlLogger(cfg.log_jsonl, r)
         self.global_step = 0
         self.history: List[dict] = []
@@ -189,8 +199,25 @@ class Trainer:
                                self.env.world, self.cfg.data_sharding)
         return self.data.x_train[lo:hi], self.data.y_train[lo:hi]
 
+    def clip_grads(self) -> None:
+        """Clip this worker's gradient buffer in place (the Python-driven step paths); the
+        norm and the coefficient stay in ``clip_out``."""
+        if self.grads.is_cuda:
+            from ..ops import native
+            native.ops().clip_grads(self.grads, self.clip_ranges, self.cfg.clip_norm,
+                                    self.clip_out)
+        else:
+            norm, coef = clip_ops.clip_grads_(self.grads, self.clip_ranges, self.cfg.clip_norm)
+            self.clip_out[0], self.clip_out[1] = norm, coef
+
+    def last_grad_norm(self) -> Optional[float]:
+        """The global norm of the last step's gradient before clipping (None with clipping
+        off).  Reads the device buffer: call it where the trainer synchronises anyway."""
+        return None if self.clip_out is None else float(self.clip_out[0])
+
     def train_step(self, step: int) -> None:
         cfg = self.cfg
+        clip = self.clip_out is not None
         x, y = self.batch(step)
         seed = rng.step_seed(cfg.seed, self.env.rank, self.global_step)
         if cfg.mode == "async" and not self.async_as_sync and \
@@ -200,6 +227,8 @@ class Trainer:
         elif cfg.mode == "async" and not self.async_as_sync:
             with trace_range("fwd_bwd"):
                 self.engine.forward_backward(x, y, cfg.keep_prob, seed)
+            if clip:
+                self.clip_grads()
             with trace_range("push_pull"):
                 self.exchange.push_pull()
         elif getattr(self.exchange, "native", False):
@@ -209,7 +238,10 @@ class Trainer:
             ex = self.exchange
             ex.begin_step()
             with trace_range("fwd_bwd"):
-                self.engine.forward_backward(x, y, cfg.keep_prob, seed, on_segment=ex.grads_ready)
+                self.engine.forward_backward(x, y, cfg.keep_prob, seed,
+                                             on_segment=None if clip else ex.grads_ready)
+            if clip:
+                self.clip_grads()
             with trace_range("exchange"):
                 ex.finish_step()
         self.global_step += 1
@@ -287,8 +319,11 @@ class Trainer:
                 line = (metrics.single_progress(meta["epoch"], meta["cnt"], acc) if single else
                         metrics.worker_progress(env.rank, meta["epoch"], meta["cnt"], acc))
                 metrics.emit(line)
+            extra = {}
+            if self.clip_out is not None and aeval is None:  # (synchronised just before)
+                extra["grad_norm"] = self.last_grad_norm()
             self.log.log(event="eval", epoch=meta["epoch"], batch=meta["cnt"], acc=acc,
-                         wall=wall, step=meta["step"])
+                         wall=wall, step=meta["step"], **extra)
             self.history.append({"step": meta["step"], "acc": acc, "wall": wall})
             if cfg.target_acc is not None and t_target is None and acc >= cfg.target_acc:
                 t_target = wall
@@ -364,6 +399,8 @@ class Trainer:
         summary = dict(final_acc=acc, cpu_time=cpu_t, wall_time=wall_t, train_wall=train_wall,
                        images=imgs, images_per_s=imgs / max(train_wall, 1e-9),
                        time_to_target=t_target, steps=self.global_step, plan=self.plan.describe())
+        if self.clip_out is not None:
+            summary["grad_norm"] = self.last_grad_norm()
         self.log.log(event="final", **summary)
         if asyncx:
             self.exchange.close()
