@@ -22,13 +22,15 @@ class TrainConfig:
     num_ps: Optional[int] = None    # default: one PS per worker process (sharded), 1 for 'none'
     epochs: int = 1
     batch_size: int = 100
-    steps: Optional[int] = None     # steps per epoch (default total_batch // batch_size = 500)
+    steps: Optional[int] = None     # steps per epoch (default total_batch // (batch_size *
+                                    # accum_steps) = 500)
     lr: float = 1e-4
     optimizer: str = "adam"         # adam | momentum | sgd
     momentum: float = 0.9
     weight_decay: float = 0.0       # decoupled (AdamW / SGDW): w -= lr * wd * w before each update
     nesterov: bool = False          # momentum only: step along mu * m' + g
     clip_norm: float = 0.0          # clip each worker's gradient to this global norm; 0 = off
+    accum_steps: int = 1            # micro-batches of batch_size per step (one update); 1 = off
     keep_prob: float = 0.5
     eval_every: int = 10            # 0 disables periodic eval
     data: str = "synthetic"
@@ -60,6 +62,7 @@ class TrainConfig:
     def __post_init__(self):
         check_optimizer_options(self.optimizer, self.momentum, self.weight_decay, self.nesterov)
         check_clip_norm(self.clip_norm)
+        check_accum_steps(self.accum_steps)
 
     def to_dict(self):
         return asdict(self)
@@ -80,6 +83,12 @@ def check_clip_norm(clip_norm: float) -> None:
     """Refuse a clip norm that is negative (or not a number); 0 switches clipping off."""
     if not clip_norm >= 0.0:
         raise ValueError(f"--clip-norm must not be negative (got {clip_norm})")
+
+
+def check_accum_steps(accum_steps: int) -> None:
+    """Refuse a micro-batch count below 1 (or not an integer); 1 switches accumulation off."""
+    from .ops.accum import check_accum_steps as check
+    check(accum_steps)
 
 
 def add_args(p: argparse.ArgumentParser, mode_default: str = "sync") -> argparse.ArgumentParser:
@@ -109,6 +118,13 @@ def add_args(p: argparse.ArgumentParser, mode_default: str = "sync") -> argparse
                    help="clip each worker's mini-batch gradient to this global norm before it is "
                         "scaled, pushed, reduced or applied (tf.clip_by_global_norm on the "
                         "worker); the step then runs without backward/exchange overlap; 0 = off")
+    p.add_argument("--accum-steps", type=int, default=d.accum_steps,
+                   help="micro-batches of --batch-size images per step: each worker sums their "
+                        "gradients on the device and pushes, reduces or applies only their mean "
+                        "(an effective batch of K * B per worker, one update and one exchange "
+                        "per K backward passes); steps, --eval-every, --checkpoint-every and "
+                        "--max-steps stay in updates; K > 1 runs without backward/exchange "
+                        "overlap; 1 = off")
     p.add_argument("--keep-prob", type=float, default=d.keep_prob)
     p.add_argument("--eval-every", type=int, default=d.eval_every)
     p.add_argument("--data", default=d.data)
@@ -155,7 +171,7 @@ def from_args(a: argparse.Namespace) -> TrainConfig:
         mode=mode, shard=shard, num_ps=a.num_ps, epochs=a.epochs, batch_size=a.batch_size,
         steps=a.steps, lr=a.lr, optimizer=a.optimizer, momentum=a.momentum,
         weight_decay=a.weight_decay, nesterov=a.nesterov, clip_norm=a.clip_norm,
-        keep_prob=a.keep_prob,
+        accum_steps=a.accum_steps, keep_prob=a.keep_prob,
         eval_every=a.eval_every, data=a.data, data_sharding=a.data_sharding,
         grad_reduce=a.grad_reduce, ref_quirks=a.ref_quirks, seed=a.seed, engine=a.engine,
         graph=a.graph and not a.no_graph, native_exchange=not a.no_native_exchange,

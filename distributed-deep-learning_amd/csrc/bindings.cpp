@@ -120,6 +120,51 @@ void clip_grads(at::Tensor grads, std::vector<std::pair<int64_t, int64_t>> range
                    (int)max_grid);
 }
 
+// Gradient accumulation (kernels/accum.hip).  acc: the fp32 accumulator, the size of grads and at
+// the same offset from a 16-byte boundary.
+void check_accum_pair(const at::Tensor& grads, const at::Tensor& acc) {
+  check_f32_cuda(grads, "grads");
+  check_f32_cuda(acc, "acc");
+  TORCH_CHECK(acc.numel() == grads.numel(), "accum: acc must have the size of grads");
+  TORCH_CHECK(acc.device() == grads.device(), "accum: acc and grads on different devices");
+  TORCH_CHECK(acc.data_ptr<float>() != grads.data_ptr<float>(), "accum: acc is grads");
+  TORCH_CHECK(((reinterpret_cast<uintptr_t>(acc.data_ptr<float>()) ^
+                reinterpret_cast<uintptr_t>(grads.data_ptr<float>())) & 15) == 0,
+              "accum: acc and grads differ in 16-byte alignment");
+}
+// A runner's accumulation site: the table, K and the accumulator it keeps alive
+struct PyAccumSite {
+  ddl::AccumSite site;
+  at::Tensor keep;
+  void set(int64_t k, const at::Tensor& grads,
+           const std::vector<std::pair<int64_t, int64_t>>& ranges,
+           c10::optional<at::Tensor> acc) {
+    TORCH_CHECK(k >= 1 && k <= (1 << 20), "set_accum: K must be at least 1");
+    site = ddl::AccumSite();
+    keep = at::Tensor();
+    if (k == 1) return;
+    TORCH_CHECK(acc.has_value(), "set_accum: K > 1 needs an accumulator");
+    check_accum_pair(grads, *acc);
+    site.ranges = clip_table(grads, ranges);
+    site.k = (int)k;
+    site.acc = acc->data_ptr<float>();
+    keep = *acc;
+  }
+};
+
+// Stand-alone: one pass of mode 0 (acc := grads), 1 (acc += grads) or 2 (grads := (acc + grads) *
+// (float)(1 / k)) over `ranges` (no host sync, no allocation)
+void accum_grads(at::Tensor grads, at::Tensor acc, std::vector<std::pair<int64_t, int64_t>> ranges,
+                 int64_t mode, int64_t k, int64_t max_grid) {
+  TORCH_CHECK(k >= 2 && k <= (1 << 20), "accum_grads: K must be at least 2");
+  TORCH_CHECK(mode >= 0 && mode <= 2, "accum_grads: mode 0 (first), 1 (add) or 2 (finish)");
+  check_accum_pair(grads, acc);
+  const ddl::ClipRanges t = clip_table(grads, ranges);
+  c10::hip::HIPGuard guard(grads.device().index());
+  ddl::launch_accum(t, grads.data_ptr<float>(), acc.data_ptr<float>(), (int)mode, (int)k,
+                    cur_stream(), (int)max_grid);
+}
+
 // Python-facing wrapper of ddl::Engine: owns the workspace tensor.
 class PyEngine {
  public:
@@ -655,6 +700,18 @@ class PyAsyncRunner {
     py::gil_scoped_release nogil;  // the host wait for the previous round
     r_->step(xp, lp, B, (uint32_t)(seed & 0xFFFFFFFF), st, timeout_s);
   }
+  // a non-final micro-batch of an accumulated round (set_accum)
+  void accumulate(at::Tensor x, at::Tensor labels, int64_t seed, double timeout_s) {
+    eng_.check_batch(x);
+    TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_cuda(), "labels must be int64 GPU");
+    TORCH_CHECK(labels.numel() == x.size(0), "labels/batch size mismatch");
+    const float* xp = x.data_ptr<float>();
+    const int64_t* lp = labels.data_ptr<int64_t>();
+    const int B = (int)x.size(0);
+    hipStream_t st = cur_stream();
+    py::gil_scoped_release nogil;  // the host wait for the previous round
+    r_->accumulate(xp, lp, B, (uint32_t)(seed & 0xFFFFFFFF), st, timeout_s);
+  }
   void finish(double timeout_s) {
     py::gil_scoped_release nogil;
     r_->finish(timeout_s);
@@ -666,6 +723,12 @@ class PyAsyncRunner {
   void set_clip(double max_norm, std::vector<std::pair<int64_t, int64_t>> ranges, at::Tensor out) {
     clip_.set(max_norm, grads_, ranges, out);
     r_->set_clip(clip_.site);
+  }
+  // every round's gradient is the mean over k micro-batches: k - 1 accumulate(), then step()
+  void set_accum(int64_t k, std::vector<std::pair<int64_t, int64_t>> ranges,
+                 c10::optional<at::Tensor> acc) {
+    accum_.set(k, grads_, ranges, acc);
+    r_->set_accum(accum_.site);
   }
   // ps: list of (ps id, private params, m, v, t), every PS (W = 1, Adam)
   void set_inline(py::list ps, double lr, double b1, double b2, double eps, double scale,
@@ -702,6 +765,7 @@ class PyAsyncRunner {
   PyEngine& eng_;
   at::Tensor grads_;
   PyClipSite clip_;
+  PyAccumSite accum_;
   std::vector<at::Tensor> keep_;
   std::unique_ptr<ddl::AsyncRunner> r_;
 };
@@ -806,6 +870,20 @@ class PyRunner {
     clip_.set(max_norm, grads_, ranges, out);
     r_->set_clip(clip_.site);
   }
+  // every step's gradient is the mean over k micro-batches: k - 1 accumulate(), then step()
+  void set_accum(int64_t k, std::vector<std::pair<int64_t, int64_t>> ranges,
+                 c10::optional<at::Tensor> acc) {
+    accum_.set(k, grads_, ranges, acc);
+    r_->set_accum(accum_.site);
+  }
+  // a non-final micro-batch of an accumulated step (set_accum)
+  void accumulate(at::Tensor x, at::Tensor labels, int64_t seed) {
+    eng_.check_batch(x);
+    TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_cuda(), "labels must be int64 GPU");
+    TORCH_CHECK(labels.numel() == x.size(0), "labels/batch size mismatch");
+    r_->accumulate(x.data_ptr<float>(), labels.data_ptr<int64_t>(), (int)x.size(0),
+                   (uint32_t)(seed & 0xFFFFFFFF), cur_stream());
+  }
   void set_local_on_main(bool on) { r_->set_local_on_main(on); }
   void set_last_on_main(bool on) { r_->set_last_on_main(on); }
   void set_ready_flags(int64_t mode) { r_->set_ready_flags((int)mode); }
@@ -844,6 +922,7 @@ class PyRunner {
   std::vector<at::Tensor> keep_;
   std::vector<float> lr_;
   PyClipSite clip_;
+  PyAccumSite accum_;
   std::unique_ptr<ddl::SyncRunner> r_;
   int64_t world_;
   PyPeer* peer_keep_ = nullptr;
@@ -864,6 +943,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("clip_grads", &clip_grads,
         "Clip grads in place by the global norm over `ranges` [(lo, n)]; out <- {norm, coef}",
         py::arg("grads"), py::arg("ranges"), py::arg("max_norm"), py::arg("out"),
+        py::arg("max_grid") = 0);
+  m.def("accum_grads", &accum_grads,
+        "One accumulation pass over `ranges` [(lo, n)]: mode 0 acc := grads, 1 acc += grads, "
+        "2 grads := (acc + grads) * float32(1 / k)",
+        py::arg("grads"), py::arg("acc"), py::arg("ranges"), py::arg("mode"), py::arg("k"),
         py::arg("max_grid") = 0);
   m.attr("CLIP_CHUNK") = (int)ddl::kClipChunk;
   m.attr("CLIP_SLOTS") = (int)ddl::kClipSlots;
@@ -978,6 +1062,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("weight_decay") = 0.0, py::arg("nesterov") = false)
       .def("set_scale", &PyRunner::set_scale)
       .def("set_clip", &PyRunner::set_clip, py::arg("max_norm"), py::arg("ranges"), py::arg("out"))
+      .def("set_accum", &PyRunner::set_accum, py::arg("k"), py::arg("ranges"), py::arg("acc"))
+      .def("accumulate", &PyRunner::accumulate, py::arg("x"), py::arg("labels"), py::arg("seed"))
       .def("set_local_on_main", &PyRunner::set_local_on_main)
       .def("set_last_on_main", &PyRunner::set_last_on_main)
       .def("set_use_tail", &PyRunner::set_use_tail)
@@ -1061,6 +1147,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("set_gate", &PyAsyncRunner::set_gate)
       .def("set_clip", &PyAsyncRunner::set_clip, py::arg("max_norm"), py::arg("ranges"),
            py::arg("out"))
+      .def("set_accum", &PyAsyncRunner::set_accum, py::arg("k"), py::arg("ranges"),
+           py::arg("acc"))
+      .def("accumulate", &PyAsyncRunner::accumulate, py::arg("x"), py::arg("labels"),
+           py::arg("seed"), py::arg("timeout_s") = 600.0)
       .def("set_inline", &PyAsyncRunner::set_inline, py::arg("ps"), py::arg("lr"), py::arg("b1"),
            py::arg("b2"), py::arg("eps"), py::arg("scale"), py::arg("provenance"),
            py::arg("weight_decay") = 0.0)

@@ -54,6 +54,43 @@ struct ClipSite {
   }
 };
 
+// ---- gradient accumulation over K micro-batches (accum.hip) ---------------------------------
+// over the ranges of g and of the accumulator acc (same size, same 16-byte alignment):
+//   kAccumFirst  acc := g (bits copied)      kAccumAdd  acc := acc + g
+//   kAccumFinish g := (acc + g) * (float)(1.0 / k)
+// One launch, no host sync; the bits do not depend on max_grid.
+enum { kAccumFirst = 0, kAccumAdd = 1, kAccumFinish = 2 };
+void launch_accum(const ClipRanges& t, float* g, float* acc, int mode, int k, hipStream_t st,
+                  int max_grid = 0);
+// one accumulation site of a step runner (set_accum): the table, K, the caller's accumulator and
+// the micro-batches accumulated so far in the open step
+struct AccumSite {
+  ClipRanges ranges;
+  int k = 1;                     // 1: off
+  float* acc = nullptr;
+  int done = 0;
+  bool on() const { return k > 1; }
+  // a non-final micro-batch's gradient is in g
+  void accumulate(float* g, hipStream_t st) {
+    launch_accum(ranges, g, acc, done == 0 ? kAccumFirst : kAccumAdd, k, st);
+    ++done;
+  }
+  // the final micro-batch's gradient is in g: g <- the mean over the K micro-batches
+  void finish(float* g, hipStream_t st) {
+    launch_accum(ranges, g, acc, kAccumFinish, k, st);
+    done = 0;
+  }
+  // refuse a micro-batch out of turn (`final`: the step's last)
+  void expect(bool final) const {
+    if (!on()) {
+      if (!final) throw std::invalid_argument("accumulate(): no accumulation set (set_accum)");
+      return;
+    }
+    if (final ? done != k - 1 : done >= k - 1)
+      throw std::invalid_argument("accumulation: a step is K - 1 accumulate() calls, then step()");
+  }
+};
+
 // ---- conv1 forward as a direct LDS-staged kernel (conv1.hip) --------------------------------
 // x [B,784], w [25,32], bias [32] -> pooled p1 [B,18,18,32] (halo layout) + codes [B,14,14,32]
 void launch_conv1_fwd(const float* x, const float* w, const float* bias, float* out,
@@ -560,6 +597,14 @@ class AsyncRunner {
   // the whole backward runs first, with no tails, then the clip, then the pushes / applies in
   // segment order.  max_norm 0: off
   void set_clip(const ClipSite& c) { clip_ = c; }
+  // accumulate the gradient over K micro-batches (accum.hip): K - 1 accumulate() calls, then
+  // step(), whose backward runs whole, with no tails, ahead of the finish pass (the mean into the
+  // gradient buffer), the clip if on, then the pushes / applies in segment order.  k 1: off
+  void set_accum(const AccumSite& a) { accum_ = a; }
+  // a non-final micro-batch: the start-of-step wait for the previous round's parameters (board
+  // path), forward, the whole backward, the accumulate pass; no round, push, gate or apply
+  void accumulate(const float* x, const int64_t* labels, int B, uint32_t seed, hipStream_t st,
+                  double timeout_s);
   // In-line applies (one worker, every PS hosted by it, Adam): each push is applied on the
   // compute stream as Adam tail blocks of the next segment's launch — the last segment's inside
   // conv1's weight-gradient launch — with the PS's m / v and its own step counter t, in push
@@ -578,6 +623,7 @@ class AsyncRunner {
  private:
   void wait_round(double timeout_s);
   void check_round(uint32_t e, double timeout_s);
+  void wait_params(double timeout_s);
   void step_inline(const float* x, const int64_t* labels, int B, hipStream_t st);
   UpdTail inline_tail(int seg, int f4_per_block);
   bool inline_ = false, keep_prov_ = false;
@@ -591,6 +637,7 @@ class AsyncRunner {
   bool use_tail_ = true;
   bool gate_ = true;
   ClipSite clip_;
+  AccumSite accum_;
   uint32_t gated_ = 0;  // the round the last step's gate waits for (0: none)
   hipStream_t safe_stream_ = nullptr;  // the compute stream whose priority was checked
   bool safe_checked_ = false, safe_ = false;
@@ -689,6 +736,12 @@ class SyncRunner {
   // and before anything consumes it.  The caller maps every unit to the last segment; the tail
   // and final-in-reduce placements are not taken, as with coef_ != 1.  max_norm 0: off
   void set_clip(const ClipSite& c) { clip_ = c; }
+  // accumulate the gradient over K micro-batches (accum.hip): K - 1 accumulate() calls, then
+  // step(), which runs as a clipped step does (every unit on the last segment) with the finish
+  // pass — the mean into the gradient buffer — ahead of the clip.  k 1: off
+  void set_accum(const AccumSite& a) { accum_ = a; }
+  // a non-final micro-batch: forward, the whole backward, the accumulate pass, nothing else
+  void accumulate(const float* x, const int64_t* labels, int B, uint32_t seed, hipStream_t st);
   // one synchronous training step on stream `st`; lr_t indexed by RunnerUnit::ps
   void step(const float* x, const int64_t* labels, int B, uint32_t seed, const float* lr_t,
             hipStream_t st);
@@ -764,6 +817,7 @@ class SyncRunner {
   float lr_ = 1e-4f;       // momentum's step size (Adam's lr_t comes with every step())
   float coef_ = 1.f;
   ClipSite clip_;
+  AccumSite accum_;
   // a range's parameter / optimizer-state span (state at state_off of the owning PS's m / v)
   UpdSpan span_of(const RunnerRange& r, float* m, float* v) const {
     return UpdSpan{w_ + r.lo, m + r.state_off, v ? v + r.state_off : nullptr};

@@ -86,6 +86,17 @@ void AsyncRunner::check_round(uint32_t e, double timeout_s) {
                              std::to_string(peer_->error()) + ")");
 }
 
+// The previous round's parameters are in place before a forward reads them: the gate enqueued
+// at the end of the previous step (the host checks the round before that: it ran before the
+// previous forward, so in steady state this returns at once), or a host wait
+void AsyncRunner::wait_params(double timeout_s) {
+  if (gated_ != 0) {
+    if (gated_ - 1 != epoch0_) check_round(gated_ - 1, timeout_s);
+  } else {
+    wait_round(timeout_s);
+  }
+}
+
 void AsyncRunner::set_inline(const std::vector<AsyncPsState>& ps, float lr, float b1, float b2,
                              float eps, float scale, bool provenance, float decay) {
   const int P = peer_->num_ps();
@@ -180,15 +191,17 @@ void AsyncRunner::step_inline(const float* x, const int64_t* labels, int B, hipS
                     peer_->grads() + lo, n, st);
     }
   };
-  if (clip_.on()) {
-    // the norm needs the whole backward: no tails; clip, then every segment's applies in
-    // segment order (the push order of the unclipped step)
+  if (clip_.on() || accum_.on()) {
+    // the norm (and the mean over the micro-batches) needs the whole backward: no tails; finish
+    // the accumulation, clip, then every segment's applies in segment order (the push order of
+    // the plain step)
     for (int s = 0; s < kSegments; ++s) {
       TraceRange r("ddl.bwd");
       eng_->backward_segment(s, x, labels, B, nullptr, st);
       eng_->flush_tail(st);
     }
-    clip_.launch(const_cast<float*>(peer_->grads()), st);
+    if (accum_.on()) accum_.finish(const_cast<float*>(peer_->grads()), st);
+    if (clip_.on()) clip_.launch(const_cast<float*>(peer_->grads()), st);
     for (int s = 0; s < kSegments; ++s) apply_now(s);
     return;
   }
@@ -217,6 +230,7 @@ void AsyncRunner::step_inline(const float* x, const int64_t* labels, int B, hipS
 void AsyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t seed,
                        hipStream_t st, double timeout_s) {
   TraceRange step_range("ddl.async.step");
+  accum_.expect(true);
   if (inline_) {
     eng_->seed_value = seed;
     last_st_ = st;
@@ -227,11 +241,7 @@ void AsyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t se
   // (1) the previous round's parameters are in place before the forward: the gate enqueued at
   // the end of the previous step (the host checks the round before that: it ran before the
   // previous forward, so in steady state this returns at once), or a host wait
-  if (gated_ != 0) {
-    if (gated_ - 1 != epoch0_) check_round(gated_ - 1, timeout_s);
-  } else {
-    wait_round(timeout_s);
-  }
+  wait_params(timeout_s);
   ++epoch_;
   eng_->seed_value = seed;
   {
@@ -253,16 +263,18 @@ void AsyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t se
   int last = kSegments - 1;
   while (last > 0 && seg_ps_[last].empty()) --last;
   gated_ = 0;
-  const bool clip = clip_.on();
+  const bool clip = clip_.on() || accum_.on();
   if (clip) {
-    // a clipped round: the whole backward with no push tails, the clip, then the pushes below
-    // in segment order (push kernels of their own; the last carries the gate)
+    // a clipped (or accumulated) round: the whole backward with no push tails, the mean over the
+    // micro-batches, the clip, then the pushes below in segment order (push kernels of their
+    // own; the last carries the gate)
     for (int s = 0; s < kSegments; ++s) {
       TraceRange r("ddl.bwd");
       eng_->backward_segment(s, x, labels, B, nullptr, st);
     }
     eng_->flush_tail(st);
-    clip_.launch(const_cast<float*>(peer_->grads()), st);
+    if (accum_.on()) accum_.finish(const_cast<float*>(peer_->grads()), st);
+    if (clip_.on()) clip_.launch(const_cast<float*>(peer_->grads()), st);
   }
   for (int s = 0; s < kSegments; ++s) {
     if (!clip) {
@@ -291,6 +303,32 @@ void AsyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t se
     peer_->gate(epoch_, st);
     gated_ = epoch_;
   }
+}
+
+// A non-final micro-batch of an accumulated round (set_accum): the parameters it reads are the
+// previous round's, as the round's final micro-batch will read them; its gradient goes into the
+// accumulator.  No round is opened: no board post, push, gate or apply.
+void AsyncRunner::accumulate(const float* x, const int64_t* labels, int B, uint32_t seed,
+                             hipStream_t st, double timeout_s) {
+  TraceRange step_range("ddl.async.accumulate");
+  accum_.expect(false);
+  if (inline_) {
+    last_st_ = st;
+    stepped_ = true;
+  } else {
+    wait_params(timeout_s);
+  }
+  eng_->seed_value = seed;
+  {
+    TraceRange r("ddl.fwd");
+    eng_->forward(x, B, nullptr, true, st, /*defer_fc2=*/true);
+  }
+  for (int s = 0; s < kSegments; ++s) {
+    TraceRange r("ddl.bwd");
+    eng_->backward_segment(s, x, labels, B, nullptr, st);
+  }
+  eng_->flush_tail(st);
+  accum_.accumulate(const_cast<float*>(peer_->grads()), st);
 }
 
 void AsyncRunner::finish(double timeout_s) {

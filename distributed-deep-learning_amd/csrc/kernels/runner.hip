@@ -384,7 +384,10 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
   if (closed_) throw std::runtime_error("sync runner: step() after close()");
   TraceRange step_range("ddl.step");
   upd_launches_ = eng_->update_launches = 0;  // (host counters: update_launches())
-  if (clip_.on())
+  accum_.expect(true);
+  // (an accumulated step's final micro-batch runs as a clipped step does)
+  const bool whole = clip_.on() || accum_.on();
+  if (whole)
     for (const auto& u : units_)
       if (u.seg != kSegments - 1)
         throw std::invalid_argument("sync runner: a clipped step needs every unit on the last segment");
@@ -401,7 +404,7 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
   // (Adam needs every piece's v; momentum / SGD have none and form none)
   if (all_local_ && local_on_main_ && use_tail_ && tail_ok_ &&
       (rule_.kind == kUpdMomentum || tail_v_ok_) &&
-      coef_ == 1.f && !clip_.on()) {
+      coef_ == 1.f && !whole) {
     // segment s-1's update rides in segment s's dual launch (flushed as a launch of its own
     // if the segment had no dual launch to take it); the last segment's follows the backward
     for (int s = 0; s < kSegments; ++s) {
@@ -432,6 +435,10 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
     for (int s = 0; s < kSegments; ++s) {
       TraceRange r(kBwdRange[s]);
       eng_->backward_segment(s, x, labels, B, seed, st);
+    }
+    if (accum_.on()) {
+      eng_->flush_tail(st);
+      accum_.finish(g_, st);  // the mean over the K micro-batches, ahead of the clip
     }
     if (clip_.on()) clip_.launch(g_, st);
     TraceRange r("ddl.update");
@@ -471,7 +478,7 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
     // than a marker packet behind them
     // (a clipped step's gradients are complete only after the clip, which follows the segment's
     // launches: a marker record behind it, not an event bound to the segment's last launch)
-    const bool bind = ext_event_ && !on_main && seg_offstream_[s] && !flag && !clip_.on();
+    const bool bind = ext_event_ && !on_main && seg_offstream_[s] && !flag && !whole;
     // bound to the segment's LAST launch (its count is learned from the previous step; a
     // wrong or unknown count falls back to a marker record below, which supersedes the binding)
     bool marker = !bind;
@@ -488,6 +495,10 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
     }
     // every unit is the last segment's (checked above): the worker's own clipped gradient is
     // what every exchange and update below reads
+    if (accum_.on() && s == kSegments - 1) {
+      eng_->flush_tail(st);
+      accum_.finish(g_, st);
+    }
     if (clip_.on() && s == kSegments - 1) clip_.launch(g_, st);
     TraceRange ex_range(kExRange[s]);
     hipStream_t xs = on_main ? st : cs_;
@@ -542,6 +553,27 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
     HIP_CHECK(hipEventRecord(done_ev_, cs_));
     HIP_CHECK(hipStreamWaitEvent(st, done_ev_, 0));
   }
+}
+
+// A non-final micro-batch of an accumulated step (set_accum): its gradient goes into the
+// accumulator and nowhere else.  No epoch, READY epoch, comm stream, exchange or update.
+void SyncRunner::accumulate(const float* x, const int64_t* labels, int B, uint32_t seed_value,
+                            hipStream_t st) {
+  if (closed_) throw std::runtime_error("sync runner: accumulate() after close()");
+  accum_.expect(false);
+  TraceRange step_range("ddl.accumulate");
+  upd_launches_ = eng_->update_launches = 0;
+  eng_->seed_value = seed_value;
+  {
+    TraceRange r("ddl.fwd");
+    eng_->forward(x, B, nullptr, true, st, /*defer_fc2=*/true);
+  }
+  for (int s = 0; s < kSegments; ++s) {
+    TraceRange r(kBwdRange[s]);
+    eng_->backward_segment(s, x, labels, B, nullptr, st);
+  }
+  eng_->flush_tail(st);
+  accum_.accumulate(g_, st);
 }
 
 // The READY gate waits on the comm stream for a kernel of `st`: only safe when `st` cannot share

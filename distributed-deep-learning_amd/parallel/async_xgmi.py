@@ -136,12 +136,13 @@ class AsyncPeerExchange:
         self.inline_ok = False
 
     # -- the native worker step ----------------------------------------------------------------------
-    def attach_runner(self, engine, segments) -> None:
+    def attach_runner(self, engine, segments, accum=None) -> None:
         """Issue the worker step from C++ (csrc/kernels/async_runner.hip) — forward, the backward
         segments with each PS's push launched as soon as its range is complete (the push posts
         itself on the arrival board), the previous round's pull as a host wait at the start of
         the step — when the engine is the HIP one.  DDL_ASYNC_NATIVE=0 keeps the Python
-        push_pull path."""
+        push_pull path.  accum: the trainer's (K, ranges, accumulator) under --accum-steps: the
+        runner then takes K - 1 native_accumulate() calls ahead of every native_step()."""
         from ..models.layout import TENSORS
         if getattr(engine, "name", "") != "hip" or os.environ.get("DDL_ASYNC_NATIVE", "1") != "1":
             return
@@ -153,6 +154,8 @@ class AsyncPeerExchange:
             seg_of_ps.append(max(seg_of[t] for t in ts))
         self.runner = native.ops().AsyncRunner(engine.eng, self.peer, self.env.world,
                                                self.env.rank, seg_of_ps, self.epoch)
+        if accum is not None:
+            self.runner.set_accum(*accum)
         # one worker hosting every PS (W = 1) with Adam: the pushes are applied in-line, as
         # tail blocks of the next backward launch (async_runner.hip set_inline); start() turns
         # it on once the PS state is final (a resume loads it after this point).
@@ -165,6 +168,13 @@ class AsyncPeerExchange:
         self.runner.step(x if x.is_contiguous() else x.contiguous(), y, seed & 0xFFFFFFFF,
                          self.timeout_s)
         self.epoch += 1
+
+    def native_accumulate(self, engine, x, y, keep_prob: float, seed: int) -> None:
+        """A non-final micro-batch of an accumulated round: no round is opened, nothing is
+        pushed (the round counter stays)."""
+        engine._set_keep(keep_prob)
+        self.runner.accumulate(x if x.is_contiguous() else x.contiguous(), y, seed & 0xFFFFFFFF,
+                               self.timeout_s)
 
     def drain_round(self) -> None:
         """The round in flight (native step) has come back: this worker's parameters are final

@@ -81,7 +81,8 @@ class NativeSyncExchange(SyncExchange):
                  grad_reduce: str = "sum", ref_quirks: bool = False, overlap: bool = True,
                  optimizer: str = "adam", hyper=None, momentum: float = 0.9,
                  force_collectives: bool = False, backend: str = "rccl",
-                 weight_decay: float = 0.0, nesterov: bool = False, clip=None):
+                 weight_decay: float = 0.0, nesterov: bool = False, clip=None,
+                 accum=None):
         if optimizer not in ("adam", "momentum", "sgd"):
             raise NativeUnavailable(f"native runner has no '{optimizer}' update")
         if optimizer == "sgd":
@@ -180,6 +181,12 @@ class NativeSyncExchange(SyncExchange):
             if overlap:
                 raise ValueError("a clipped step has no per-segment hand-off: overlap=False")
             self.runner.set_clip(*clip)
+        # accum = (K, [(lo, n)] payload ranges, the accumulator): K - 1 accumulate() calls, then
+        # step(), whose final micro-batch runs as a clipped step does (overlap=False again)
+        if accum is not None:
+            if overlap:
+                raise ValueError("an accumulated step has no per-segment hand-off: overlap=False")
+            self.runner.set_accum(*accum)
         # A/B knob: DDL_LAST_ON_MAIN=0 puts the last segment's collectives back on the comm
         # stream (one event hop more on the critical path of every W > 1 step)
         self.runner.set_last_on_main(os.environ.get("DDL_LAST_ON_MAIN", "1") != "0")
@@ -332,6 +339,14 @@ class NativeSyncExchange(SyncExchange):
         if self.env.world > 1 and self._n % 64 == 0:
             self.check()
 
+    def accumulate(self, x: torch.Tensor, labels: torch.Tensor, keep_prob: float,
+                   seed: int) -> None:
+        """A non-final micro-batch of an accumulated step: forward, backward and the
+        accumulate pass.  No PS counter advances and nothing is exchanged or updated."""
+        self.engine._set_keep(keep_prob)
+        self.runner.accumulate(x if x.is_contiguous() else x.contiguous(), labels,
+                               seed & 0xFFFFFFFF)
+
     # -- the READY-flag hand-off, proven per job (VERDICT r4 item 4) ------------------------------
     def _snapshot(self):
         srv = {p: (ps.m.clone(), None if ps.v is None else ps.v.clone(), ps.t, ps.updates)
@@ -482,13 +497,16 @@ def handoff_vote(env, digest_events: str, digest_flags: str) -> dict:
 
 
 def make_sync_exchange(plan, env, params, grads, segments, servers, engine, cfg, hyper,
-                       clip=None):
+                       clip=None, accum=None):
     """Native runner when it applies (HIP engine, sync, adam/momentum/sgd), else the Python
     exchange.  On a multi-GPU job the choice is collective (self-test votes).  clip: the
     trainer's (max_norm, ranges, out) when --clip-norm is on; the native runner then clips
     itself, the Python exchange's caller clips between the backward and finish_step().  Either
-    way nothing is handed over per segment (overlap off)."""
-    overlap = cfg.overlap and clip is None
+    way nothing is handed over per segment (overlap off).  accum: the trainer's (K, ranges,
+    accumulator) when --accum-steps is above 1, handed through in the same way: the native
+    runner accumulates itself, the Python exchange's caller between the backward and
+    finish_step(), and overlap is off."""
+    overlap = cfg.overlap and clip is None and accum is None
     if cfg.native_exchange:
         try:
             backend = cfg.exchange_backend if cfg.exchange_backend != "auto" else "rccl"
@@ -497,7 +515,7 @@ def make_sync_exchange(plan, env, params, grads, segments, servers, engine, cfg,
                                       cfg.optimizer, hyper, cfg.momentum,
                                       force_collectives=cfg.force_collectives, backend=backend,
                                       weight_decay=cfg.weight_decay, nesterov=cfg.nesterov,
-                                      clip=clip)
+                                      clip=clip, accum=accum)
         except NativeUnavailable as e:
             if env.rank == 0 and getattr(engine, "name", "") == "hip":
                 print(f"[ddl_amd] native sync runner unavailable ({e}); using the Python "

@@ -27,6 +27,7 @@ from ..models import make_engine, engine_segments
 from ..models.mnist_cnn import init_params_
 from ..ops import rng
 from ..ops import clip as clip_ops
+from ..ops import accum as accum_ops
 from ..ops.adam import AdamHyper
 from ..utils import metrics
 from ..utils.data import Dataset, get_dataset, batch_indices
@@ -129,7 +130,9 @@ class Trainer:
                                               nesterov=cfg.nesterov)
         self.data = dataset if dataset is not None else get_dataset(cfg.data, seed=1234)
         self.data = self.data.to(dev)
-        self.steps = cfg.steps or (self.data.total_batch // cfg.batch_size)
+        # a step is one update: it consumes accum_steps micro-batches of batch_size images
+        K = cfg.accum_steps
+        self.steps = cfg.steps or (self.data.total_batch // (cfg.batch_size * K))
         # Clipping by the global norm (ops/clip.py, csrc/kernels/clip.hip): the worker's own
         # gradient, before anything else reads it.  The norm needs the whole backward, so a
         # clipped step hands nothing over per segment: every exchange unit is the last segment's.
@@ -137,15 +140,22 @@ class Trainer:
         self.clip_out = (torch.zeros(2, dtype=torch.float32, device=dev)  # {norm, coef}
                          if cfg.clip_norm > 0 else None)
         clip = (cfg.clip_norm, self.clip_ranges, self.clip_out) if cfg.clip_norm > 0 else None
+        # Accumulation over K micro-batches (ops/accum.py, csrc/kernels/accum.hip): the sum stays
+        # in an fp32 buffer of the gradient buffer's size, allocated once; after the last
+        # micro-batch the gradient buffer holds the mean and everything downstream reads it.
+        # Like a clipped step, the final micro-batch hands nothing over per segment.
+        self.accum_buf = torch.zeros_like(self.grads) if K > 1 else None
+        accum = (K, self.clip_ranges, self.accum_buf) if K > 1 else None
         if asyncm and not self.async_as_sync:
             self.exchange = self._make_async_exchange(cfg, env)
             if hasattr(self.exchange, "attach_runner"):
-                self.exchange.attach_runner(self.engine, segs)
+                self.exchange.attach_runner(self.engine, segs, accum=accum)
                 if clip is not None and self.exchange.runner is not None:
                     self.exchange.runner.set_clip(*clip)
         else:
             self.exchange = make_sync_exchange(self.plan, env, self.params, self.grads, segs,
-                                               self.servers, self.engine, cfg, hyper, clip=clip)
+                                               self.servers, self.engine, cfg, hyper, clip=clip,
+                                               accum=accum)
         self.log = metrics.JsonlLogger(cfg.log_jsonl, r)
         self.global_step = 0
         self.history: List[dict] = []
@@ -215,35 +225,69 @@ class Trainer:
         off).  Reads the device buffer: call it where the trainer synchronises anyway."""
         return None if self.clip_out is None else float(self.clip_out[0])
 
+    def accum_grads(self, j: int) -> None:
+        """The accumulation pass after micro-batch ``j`` of the step (the Python-driven step
+        paths): the sum into ``accum_buf``, after the last one the mean into ``grads``."""
+        K = self.cfg.accum_steps
+        mode = accum_ops.mode_of(j, K)
+        if self.grads.is_cuda:
+            from ..ops import native
+            native.ops().accum_grads(self.grads, self.accum_buf, self.clip_ranges, mode, K)
+        else:
+            accum_ops.accum_grads_(self.grads, self.accum_buf, self.clip_ranges, mode, K)
+
     def train_step(self, step: int) -> None:
+        """One step = one update, from ``accum_steps`` micro-batches: micro-batch ``j`` of
+        step index ``step`` reads batch ``step * K + j`` with the dropout seed of micro-step
+        ``global_step * K + j`` (K = 1: the step's own).  Only the last one exchanges, clips
+        and updates; the others leave their gradient in the accumulator."""
         cfg = self.cfg
         clip = self.clip_out is not None
-        x, y = self.batch(step)
-        seed = rng.step_seed(cfg.seed, self.env.rank, self.global_step)
-        if cfg.mode == "async" and not self.async_as_sync and \
-                getattr(self.exchange, "runner", None) is not None:
-            with trace_range("step_native_async"):
-                self.exchange.native_step(self.engine, x, y, cfg.keep_prob, seed)
-        elif cfg.mode == "async" and not self.async_as_sync:
-            with trace_range("fwd_bwd"):
-                self.engine.forward_backward(x, y, cfg.keep_prob, seed)
-            if clip:
-                self.clip_grads()
-            with trace_range("push_pull"):
-                self.exchange.push_pull()
-        elif getattr(self.exchange, "native", False):
-            with trace_range("step_native"):
-                self.exchange.step(x, y, cfg.keep_prob, seed)
-        else:
-            ex = self.exchange
-            ex.begin_step()
-            with trace_range("fwd_bwd"):
-                self.engine.forward_backward(x, y, cfg.keep_prob, seed,
-                                             on_segment=None if clip else ex.grads_ready)
-            if clip:
-                self.clip_grads()
-            with trace_range("exchange"):
-                ex.finish_step()
+        K = cfg.accum_steps
+        ex = self.exchange
+        for j in range(K):
+            final = j == K - 1
+            x, y = self.batch(step * K + j)
+            seed = rng.step_seed(cfg.seed, self.env.rank, self.global_step * K + j)
+            if cfg.mode == "async" and not self.async_as_sync and \
+                    getattr(ex, "runner", None) is not None:
+                with trace_range("step_native_async"):
+                    if final:
+                        ex.native_step(self.engine, x, y, cfg.keep_prob, seed)
+                    else:
+                        ex.native_accumulate(self.engine, x, y, cfg.keep_prob, seed)
+            elif cfg.mode == "async" and not self.async_as_sync:
+                with trace_range("fwd_bwd"):
+                    self.engine.forward_backward(x, y, cfg.keep_prob, seed)
+                if K > 1:
+                    self.accum_grads(j)
+                if not final:
+                    continue
+                if clip:
+                    self.clip_grads()
+                with trace_range("push_pull"):
+                    ex.push_pull()
+            elif getattr(ex, "native", False):
+                with trace_range("step_native"):
+                    if final:
+                        ex.step(x, y, cfg.keep_prob, seed)
+                    else:
+                        ex.accumulate(x, y, cfg.keep_prob, seed)
+            else:
+                if j == 0:
+                    ex.begin_step()  # one apply_gradients per step, not per micro-batch
+                with trace_range("fwd_bwd"):
+                    self.engine.forward_backward(
+                        x, y, cfg.keep_prob, seed,
+                        on_segment=None if (clip or K > 1) else ex.grads_ready)
+                if K > 1:
+                    self.accum_grads(j)
+                if not final:
+                    continue
+                if clip:
+                    self.clip_grads()
+                with trace_range("exchange"):
+                    ex.finish_step()
         self.global_step += 1
 
     def evaluate(self) -> float:
@@ -395,7 +439,8 @@ class Trainer:
         wd.stop()
         if cfg.checkpoint_dir:
             ckpt.save(self, cfg.checkpoint_dir)
-        imgs = (self.global_step - first) * cfg.batch_size  # this run's steps (resume)
+        # this run's steps (resume), each of accum_steps micro-batches
+        imgs = (self.global_step - first) * cfg.batch_size * cfg.accum_steps
         summary = dict(final_acc=acc, cpu_time=cpu_t, wall_time=wall_t, train_wall=train_wall,
                        images=imgs, images_per_s=imgs / max(train_wall, 1e-9),
                        time_to_target=t_target, steps=self.global_step, plan=self.plan.describe())

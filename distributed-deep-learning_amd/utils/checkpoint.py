@@ -8,7 +8,7 @@ slots ``/Adam`` (m), ``/Adam_1`` (v) and per-PS ``beta1_power``/``beta2_power``
 
 Layout of a checkpoint directory (safetensors, no pickle):
 
-  manifest.json                 plan, world, step, per-PS step counters
+  manifest.json                 plan, world, step, per-PS step counters, accum_steps
   worker{r}.safetensors         mnist/v{i} for worker r (sync: only worker 0)
   ps{p}.safetensors             ParameterServer/v{i}[@a:b], .../Adam, .../Adam_1,
                                 ParameterServer/beta1_power, beta2_power
@@ -98,6 +98,8 @@ def save(trainer, path: str) -> None:
         # the ranges it counted
         man = dict(policy=plan.policy, num_ps=plan.num_ps, world=env.world, mode=trainer.cfg.mode,
                    global_step=trainer.global_step, ps_t=ps_t,
+                   # (saves happen on step boundaries only: the accumulator is never saved)
+                   accum_steps=int(trainer.cfg.accum_steps),
                    ps_segments=[[list(map(int, r)) for r in plan.ps_segments(p)]
                                 for p in range(plan.num_ps)])
         with open(os.path.join(path, "manifest.json"), "w") as f:
@@ -156,6 +158,13 @@ def load(trainer, path: str) -> None:
     with open(os.path.join(path, "manifest.json")) as f:
         man = json.load(f)
     env, plan = trainer.env, trainer.plan
+    # a step's data indices and dropout seeds are functions of K: the same global step under
+    # another K is another position in the data (a manifest without the field: K = 1)
+    saved_k = int(man.get("accum_steps", 1))
+    if saved_k != int(trainer.cfg.accum_steps):
+        raise ValueError(f"checkpoint {path} was written with --accum-steps {saved_k}; resuming "
+                         f"with --accum-steps {trainer.cfg.accum_steps} would not continue that "
+                         f"run (step {man['global_step']} reads other batches and dropout seeds)")
     wf = os.path.join(path, f"worker{env.rank}.safetensors")
     if not os.path.exists(wf):
         wf = os.path.join(path, "worker0.safetensors")
