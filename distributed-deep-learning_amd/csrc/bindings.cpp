@@ -760,6 +760,7 @@ class PyAsyncRunner {
   int64_t inline_t(int64_t ps) const { return r_->inline_t((int)ps); }
   void inline_sync_ps() { r_->inline_sync_ps(cur_stream()); }
   std::vector<std::array<int64_t, 4>> inline_provenance() const { return r_->inline_provenance(); }
+  int64_t update_launches() const { return r_->update_launches(); }
 
  private:
   PyEngine& eng_;
@@ -1157,7 +1158,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("inline_on", &PyAsyncRunner::inline_on)
       .def("inline_t", &PyAsyncRunner::inline_t)
       .def("inline_sync_ps", &PyAsyncRunner::inline_sync_ps)
-      .def("inline_provenance", &PyAsyncRunner::inline_provenance);
+      .def("inline_provenance", &PyAsyncRunner::inline_provenance)
+      .def("update_launches", &PyAsyncRunner::update_launches,
+           "Stand-alone optimizer kernel launches issued for the most recent in-line step()");
 
   py::class_<PyPeer>(m, "PeerExchange")
       .def(py::init<at::Tensor, at::Tensor, int64_t, int64_t, py::list, int64_t, int64_t>(),

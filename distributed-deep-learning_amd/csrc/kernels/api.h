@@ -91,6 +91,19 @@ struct AccumSite {
   }
 };
 
+// what a step runner does to its worker's whole gradient before anything consumes it
+struct GradStage {
+  ClipSite clip;
+  AccumSite accum;
+  // the backward runs whole, nothing riding in it (an accumulated step's final micro-batch runs
+  // as a clipped step does)
+  bool whole() const { return clip.on() || accum.on(); }
+  void finish(float* g, hipStream_t st) {  // the mean over the K micro-batches, then the clip
+    if (accum.on()) accum.finish(g, st);
+    if (clip.on()) clip.launch(g, st);
+  }
+};
+
 // ---- conv1 forward as a direct LDS-staged kernel (conv1.hip) --------------------------------
 // x [B,784], w [25,32], bias [32] -> pooled p1 [B,18,18,32] (halo layout) + codes [B,14,14,32]
 void launch_conv1_fwd(const float* x, const float* w, const float* bias, float* out,
@@ -280,6 +293,64 @@ struct Engine {
   void wgrad(int op, const float* x, int B, const uint32_t* seed, hipStream_t st);
 };
 
+// ---- what the two step runners share (runner.hip) -------------------------------------------
+struct MicroBatch {  // on stream st; bwd_range: the trace range name of each backward segment
+  const float* x;
+  const int64_t* labels;
+  int B;
+  hipStream_t st;
+  const char* const* bwd_range;
+};
+// the step's forward (fc2's reduce left to the head: the backward follows)
+void run_forward(Engine& eng, const MicroBatch& mb);
+// the four backward segments with nothing riding in them, then a pending tail flushed
+void run_whole_backward(Engine& eng, const MicroBatch& mb);
+
+struct LocalUpdates {     // one worker, every update local (W = 1)
+  const UpdatePlan* plan;
+  UpdRule rule;
+  float lr;               // the momentum rule's step size
+  const float* lr_t;      // the Adam rule's, by PS
+  float* w;
+  const float* g;
+  int max_grid = 2048;    // of a stand-alone launch
+  float step(const PlanPiece& p) const { return rule.kind == kUpdMomentum ? lr : lr_t[p.ps]; }
+};
+// launch_update of each piece; returns the launches issued
+int launch_piece_updates(const LocalUpdates& u, const std::vector<PlanPiece>& pieces,
+                         hipStream_t st);
+struct RidePolicy {
+  bool rides[kPlanSegments];  // the segment is offered as a tail; else launched piece by piece
+  int first, f4_per_block;    // UpdTail's, of a tail beside a dual launch
+  bool final_in_reduce;       // offer the last segment to conv1's weight-gradient launch
+};
+// The four backward segments with segment s - 1's update as the tail of segment s's launch
+// (flushed as a launch of its own if the segment had no launch to take it) and the last segment's
+// inside conv1's weight-gradient launch when the engine takes it (engine_impl.h dual_then_b),
+// else launched after the backward.  Returns the stand-alone launches it issued itself (the
+// engine counts flushed tails: Engine::update_launches).
+int run_riding_backward(Engine& eng, const MicroBatch& mb, const LocalUpdates& u,
+                        const RidePolicy& pol);
+
+// May a wait for a kernel of stream `st` sit on stream `waiter` (null: any stream of the
+// device's greatest priority)?  Only when the two cannot share a hardware queue: HIP pools
+// hardware queues per priority, so when their priorities differ.  Queried once per `st`.
+struct WaitPlacement {
+  hipStream_t st = nullptr;
+  bool checked = false, ok = false;
+  bool safe(hipStream_t s, hipStream_t waiter) {
+    if (checked && s == st) return ok;
+    int lo = 0, hi = 0, p = 0, wp = 0;  // (the null stream is a normal-priority stream)
+    ok = hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess &&
+         (s == nullptr || hipStreamGetPriority(s, &p) == hipSuccess) &&
+         (waiter == nullptr || hipStreamGetPriority(waiter, &wp) == hipSuccess) && hi != lo &&
+         p != (waiter ? wp : hi);
+    st = s;
+    checked = true;
+    return ok;
+  }
+};
+
 // ---- native synchronous step runner (runner.hip) -------------------------------------------
 struct RunnerRange {
   int64_t lo, hi;       // plan-buffer element range [lo, hi)
@@ -359,6 +430,37 @@ struct XgmiUpdate {              // owner-side update of one bucket chunk
   float coef = 1.f;
 };
 
+// This rank's exported buffers and every rank's mapping of them: what PeerExchange and AsyncPeer
+// both own (xgmi.hip).  `tag` prefixes its error messages.
+class PeerMap {
+ public:
+  PeerMap(const char* tag, float* params, int world, int rank, double default_timeout_s);
+  // the zeroed inbox and uncached flag words, the host error word; the caller synchronizes
+  void alloc(int64_t inbox_elems, size_t flag_bytes);
+  std::string handle() const;                         // this rank's IPC handles, as bytes
+  void open(const std::vector<std::string>& handles);  // every rank's, in rank order
+  // unmap the peers' buffers (after the device has drained).  HIP leaves freeing an exported
+  // buffer undefined while a peer still has it mapped, so a process that goes on to build another
+  // exchange lets every rank unmap first: unmap_peers(), a host barrier, close().
+  void unmap_peers();
+  void close();  // drain the device, unmap, free the inbox, the flags and the error word; idempotent
+  int error() const { return err ? __atomic_load_n(err, __ATOMIC_ACQUIRE) : 0; }
+  long long timeout_ticks() const { return (long long)(timeout_s * 1e8); }  // wall_clock64: 100 MHz
+
+  XgmiTable table{};  // every rank's buffers, by rank (after open())
+  float* my_inbox = nullptr;
+  uint32_t* my_flags = nullptr;
+  int* err = nullptr;
+  double timeout_s;   // DDL_XGMI_TIMEOUT_S
+  bool opened = false;
+
+ private:
+  const char* tag_;
+  float* params_;
+  int world_, rank_;
+  void* mapped_[kXgmiMaxPeers][3] = {};
+};
+
 // The xGMI self-test's stale-L2 probe (xgmi.hip): every XCD reads every line of `a` (want null:
 // warms the eight L2s) or counts into out[0] the elements that differ from `want`
 void launch_xcd_sweep(const float* a, const float* want, int64_t n, int* out, hipStream_t st);
@@ -376,23 +478,21 @@ class PeerExchange {
   PeerExchange(float* params, const float* grads, int64_t total, int world, int rank,
                const std::vector<XgmiBucketSpec>& buckets, int max_slices, int repl_bucket = -1);
   ~PeerExchange();
-  std::string handle() const;                         // this rank's IPC handles, as bytes
-  void open(const std::vector<std::string>& handles);  // every rank's, in rank order
   // the fused push / owner update / pull of one bucket at step `epoch` (same on all ranks)
   // gated: the launch sits behind the runner's READY gate on the comm stream (checks its error
   // word before publishing anything)
   void launch(int bucket, uint32_t epoch, const XgmiUpdate& u, bool final_wait, hipStream_t st,
               bool gated = false);
-  int error() const;             // nonzero once a wait timed out (1 arrive, 2 done)
+  int error() const { return map_.error(); }  // nonzero once a wait timed out (1 arrive, 2 done)
   // the runner's READY-gate error word, checked by every bucket kernel before it publishes
   void set_gate_error(const int* w) { gate_err_ = w; }
   // unmap the peers' buffers and free this rank's (after the device has drained); idempotent
-  void close();
-  // the first half of close() alone.  HIP leaves freeing an exported buffer undefined while a
-  // peer still has it mapped, so a process that goes on to build another exchange lets every
-  // rank unmap first: unmap_peers(), a host barrier, close().  Nothing can be launched after it.
-  void unmap_peers();
-  double timeout_s() const { return timeout_s_; }
+  void close() { map_.close(); }
+  // the first half of close() alone (PeerMap::unmap_peers).  Nothing can be launched after it.
+  void unmap_peers() { map_.unmap_peers(); }
+  std::string handle() const { return map_.handle(); }
+  void open(const std::vector<std::string>& handles) { map_.open(handles); }
+  double timeout_s() const { return map_.timeout_s; }
   int num_buckets() const { return (int)bk_.size(); }
   int nslices(int b) const { return bk_[b].nslice; }
   int64_t chunk(int b) const { return bk_[b].c; }
@@ -428,16 +528,8 @@ class PeerExchange {
   int64_t total_;
   int world_, rank_;
   std::vector<Bucket> bk_;
-  float* inbox_ = nullptr;
-  int64_t inbox_elems_ = 0;
-  uint32_t* flags_ = nullptr;
-  size_t flag_bytes_ = 0;
-  int* err_ = nullptr;
+  PeerMap map_;
   const int* gate_err_ = nullptr;
-  double timeout_s_ = 60.0;
-  XgmiTable table_{};
-  void* opened_[kXgmiMaxPeers][3] = {};
-  bool opened_ok_ = false;
 };
 
 // ---- asynchronous PS over xGMI peer memory (xgmi_async.hip) ----------------------------------
@@ -471,10 +563,10 @@ class AsyncPeer {
             const std::vector<std::pair<int64_t, int64_t>>& ps_ranges,
             const std::vector<int>& ps_host, int max_slices);
   ~AsyncPeer();
-  std::string handle() const;
+  std::string handle() const { return map_.handle(); }
   void open(const std::vector<std::string>& handles);
   void close();  // unmap peers, free buffers and the shm board (after a device drain); idempotent
-  void unmap_peers();  // the first half of close() alone (PeerExchange::unmap_peers)
+  void unmap_peers() { map_.unmap_peers(); }  // the first half of close() alone (PeerMap)
   // worker: every PS shard of the gradient (x coef) into its host's inbox slot, round `epoch`
   void push_all(uint32_t epoch, float coef, hipStream_t st);
   // the same for the listed PS only (one launch); with_gate: plus the pull gate of round
@@ -500,7 +592,7 @@ class AsyncPeer {
   // optimizer state in u) and store the new shard into that worker's parameter buffer
   void apply(int ps, int worker, uint32_t epoch, const XgmiUpdate& u, float* ps_params,
              hipStream_t st);
-  int error() const;
+  int error() const { return map_.error(); }
   int num_ps() const { return nps_; }
   // PS p's range of the parameter / gradient buffers and its host
   void shard(int p, int64_t& lo, int64_t& n, int& host) const;
@@ -514,13 +606,7 @@ class AsyncPeer {
   int world_, rank_, nps_ = 0;
   AsyncTable table_;
   AsyncTable* table_dev_ = nullptr;  // the kernels' copy
-  float* inbox_ = nullptr;
-  int64_t inbox_elems_ = 0;
-  uint32_t* flags_ = nullptr;
-  int* err_ = nullptr;
-  double timeout_s_ = 60.0;
-  void* opened_[kXgmiMaxPeers][3] = {};
-  bool opened_ok_ = false;
+  PeerMap map_;
   uint32_t* done_host_ = nullptr;
   uint32_t* posted_host_ = nullptr;
   size_t done_bytes_ = 0;
@@ -596,11 +682,11 @@ class AsyncRunner {
   // clip this worker's gradient by its global norm (clip.hip) before any push or in-line apply:
   // the whole backward runs first, with no tails, then the clip, then the pushes / applies in
   // segment order.  max_norm 0: off
-  void set_clip(const ClipSite& c) { clip_ = c; }
+  void set_clip(const ClipSite& c) { stage_.clip = c; }
   // accumulate the gradient over K micro-batches (accum.hip): K - 1 accumulate() calls, then
   // step(), whose backward runs whole, with no tails, ahead of the finish pass (the mean into the
   // gradient buffer), the clip if on, then the pushes / applies in segment order.  k 1: off
-  void set_accum(const AccumSite& a) { accum_ = a; }
+  void set_accum(const AccumSite& a) { stage_.accum = a; }
   // a non-final micro-batch: the start-of-step wait for the previous round's parameters (board
   // path), forward, the whole backward, the accumulate pass; no round, push, gate or apply
   void accumulate(const float* x, const int64_t* labels, int B, uint32_t seed, hipStream_t st,
@@ -619,15 +705,19 @@ class AsyncRunner {
   void inline_sync_ps(hipStream_t st);  // worker buffer -> every PS's private copy
   // (worker, ps, round, t) per in-line apply, when provenance was asked for
   const std::vector<std::array<int64_t, 4>>& inline_provenance() const { return prov_; }
+  // stand-alone optimizer launches of the most recent in-line step (SyncRunner::update_launches)
+  int update_launches() const { return upd_launches_ + eng_->update_launches; }
 
  private:
   void wait_round(double timeout_s);
   void check_round(uint32_t e, double timeout_s);
   void wait_params(double timeout_s);
-  void step_inline(const float* x, const int64_t* labels, int B, hipStream_t st);
-  UpdTail inline_tail(int seg, int f4_per_block);
+  void step_inline(const MicroBatch& mb);
+  float* grads() const { return const_cast<float*>(peer_->grads()); }
   bool inline_ = false, keep_prov_ = false;
   std::vector<AsyncPsState> ips_;  // by PS id
+  UpdatePlan plan_;                // in-line: one piece per PS, its shard with its own m / v
+  int upd_launches_ = 0;
   UpdRule rule_;                   // Adam or AdamW (the in-line applies have no other rule)
   float lr_ = 0.f, b1_ = 0.f, b2_ = 0.f;  // widened to double for adam_step_size (update.h)
   std::vector<float> lr_t_;        // this round's TF1 Adam step size per PS
@@ -636,11 +726,9 @@ class AsyncRunner {
   bool stepped_ = false;
   bool use_tail_ = true;
   bool gate_ = true;
-  ClipSite clip_;
-  AccumSite accum_;
+  GradStage stage_;
   uint32_t gated_ = 0;  // the round the last step's gate waits for (0: none)
-  hipStream_t safe_stream_ = nullptr;  // the compute stream whose priority was checked
-  bool safe_checked_ = false, safe_ = false;
+  WaitPlacement gate_place_;  // the pull gate on the compute stream against the service stream
   Engine* eng_;
   AsyncPeer* peer_;
   int world_, rank_, device_;
@@ -735,11 +823,11 @@ class SyncRunner {
   // clip this worker's gradient by its global norm (clip.hip) after the fourth backward segment
   // and before anything consumes it.  The caller maps every unit to the last segment; the tail
   // and final-in-reduce placements are not taken, as with coef_ != 1.  max_norm 0: off
-  void set_clip(const ClipSite& c) { clip_ = c; }
+  void set_clip(const ClipSite& c) { stage_.clip = c; }
   // accumulate the gradient over K micro-batches (accum.hip): K - 1 accumulate() calls, then
   // step(), which runs as a clipped step does (every unit on the last segment) with the finish
   // pass — the mean into the gradient buffer — ahead of the clip.  k 1: off
-  void set_accum(const AccumSite& a) { accum_ = a; }
+  void set_accum(const AccumSite& a) { stage_.accum = a; }
   // a non-final micro-batch: forward, the whole backward, the accumulate pass, nothing else
   void accumulate(const float* x, const int64_t* labels, int B, uint32_t seed, hipStream_t st);
   // one synchronous training step on stream `st`; lr_t indexed by RunnerUnit::ps
@@ -805,9 +893,9 @@ class SyncRunner {
   // seg events recorded by the segment's own kernel packets (DDL_EXT_EVENT, default on)
   bool ext_event_ = true;
   hipEvent_t done_ev_ = nullptr;
-  bool gate_safe(hipStream_t st);  // `st` is not a high-priority stream (runner.hip)
-  hipStream_t gate_checked_stream_ = nullptr;
-  bool gate_checked_ = false, gate_checked_ok_ = false;
+  // the READY gate on the comm stream (the greatest priority, or the least with
+  // DDL_COMM_PRIORITY=low) waits for a kernel of the compute stream; else the event hand-off
+  WaitPlacement gate_place_;
   uint32_t* ready_ = nullptr;     // READY[segment] (uncached device memory, tail.h kind 2)
   int* ready_err_ = nullptr;      // a READY gate timed out (host memory)
   double gate_timeout_s_ = 20.0;  // DDL_XGMI_TIMEOUT_S
@@ -816,8 +904,7 @@ class SyncRunner {
   UpdRule rule_{kUpdAdam, 0.9f, 0.999f, 1e-8f, 0.9f, 1.f};  // (scale: set_scale's grad_scale)
   float lr_ = 1e-4f;       // momentum's step size (Adam's lr_t comes with every step())
   float coef_ = 1.f;
-  ClipSite clip_;
-  AccumSite accum_;
+  GradStage stage_;
   // a range's parameter / optimizer-state span (state at state_off of the owning PS's m / v)
   UpdSpan span_of(const RunnerRange& r, float* m, float* v) const {
     return UpdSpan{w_ + r.lo, m + r.state_off, v ? v + r.state_off : nullptr};
@@ -826,26 +913,13 @@ class SyncRunner {
   float step_of(float lr_t) const { return rule_.kind == kUpdMomentum ? lr_ : lr_t; }
   bool local_on_main_ = true;
   bool last_on_main_ = true;
-  struct Piece {
-    RunnerRange r;
-    int ps;
-    float* m;
-    float* v;
-  };
   bool all_local_ = false;
-  std::vector<Piece> merged_;  // coalesced LOCAL update ranges (all_local_)
-  // all_local_: the same ranges coalesced per backward segment; segment s's update rides as
-  // an optimizer tail (tail.h) in segment s+1's dual launch when every piece is 16-B vector
-  // shaped (tail_ok_), the last segment's is launched after the backward
-  std::vector<Piece> seg_pieces_[kSegments];
-  bool tail_ok_ = false;
-  bool tail_v_ok_ = false;  // ... and has a 16-B aligned v (the Adam rule; momentum has none)
+  UpdatePlan plan_;  // all_local_: where the LOCAL updates go (update_plan.h)
   bool use_tail_ = true;
   bool final_in_reduce_ = [] {
     const char* e = getenv("DDL_FINAL_IN_REDUCE");
     return !e || e[0] != '0';
   }();
-  void set_tail(int seg, const float* lr_t, int f4_per_block = 0);
 
  public:
   void set_ready_flags(int mode) { ready_flags_ = mode; }

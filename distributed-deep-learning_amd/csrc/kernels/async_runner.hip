@@ -52,6 +52,9 @@
 
 namespace ddl {
 
+static const char* const kBwdRange[AsyncRunner::kSegments] = {"ddl.bwd", "ddl.bwd", "ddl.bwd",
+                                                              "ddl.bwd"};
+
 AsyncRunner::AsyncRunner(Engine* eng, AsyncPeer* peer, int world, int rank, int device,
                          const std::vector<int>& seg_of_ps, uint32_t epoch0)
     : eng_(eng), peer_(peer), world_(world), rank_(rank), device_(device), epoch_(epoch0),
@@ -102,7 +105,6 @@ void AsyncRunner::set_inline(const std::vector<AsyncPsState>& ps, float lr, floa
   const int P = peer_->num_ps();
   if (world_ != 1) throw std::invalid_argument("async runner: in-line applies need one worker");
   if ((int)ps.size() != P) throw std::invalid_argument("async runner: in-line applies need every PS");
-  auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   std::vector<AsyncPsState> by(P, AsyncPsState{-1, nullptr, nullptr, nullptr, 0});
   for (const auto& s : ps) {
     if (s.ps < 0 || s.ps >= P || by[s.ps].ps >= 0 || !s.params || !s.m || !s.v)
@@ -111,12 +113,24 @@ void AsyncRunner::set_inline(const std::vector<AsyncPsState>& ps, float lr, floa
     int host = -1;
     peer_->shard(s.ps, lo, n, host);
     if (host != rank_) throw std::invalid_argument("async runner: in-line PS hosted elsewhere");
-    if (n % 4 || !a16(peer_->params() + lo) || !a16(peer_->grads() + lo) || !a16(s.m) ||
-        !a16(s.v))
+    if (n % 4 || !aligned16(float_at(peer_->params(), lo)) ||
+        !aligned16(float_at(peer_->grads(), lo)) || !aligned16(float_at(s.m, 0)) ||
+        !aligned16(float_at(s.v, 0)))
       throw std::invalid_argument("async runner: in-line PS buffers must be 16-B aligned");
     by[s.ps] = s;
   }
   ips_ = by;
+  // one piece per PS: its shard with its own m / v, after the segment that completes it
+  plan_ = UpdatePlan();
+  for (int sg = 0; sg < kSegments; ++sg)
+    for (int p : seg_ps_[sg]) {
+      int64_t lo = 0, n = 0;
+      int host = -1;
+      peer_->shard(p, lo, n, host);
+      plan_.add(sg, PlanPiece{lo, lo + n, 0, p, by[p].m, by[p].v});
+    }
+  plan_.finish(reinterpret_cast<uintptr_t>(peer_->params()),
+               reinterpret_cast<uintptr_t>(peer_->grads()));
   rule_ = UpdRule(kUpdAdam, b1, b2, eps, 0.f, scale, decay);
   lr_ = lr;
   b1_ = b1;
@@ -146,96 +160,42 @@ void AsyncRunner::inline_sync_ps(hipStream_t st) {
   }
 }
 
-// Segment `seg`'s PS shards as one Adam tail (tail.h kind 0); empty if they do not fit one
-UpdTail AsyncRunner::inline_tail(int seg, int f4_per_block) {
-  UpdTail t;
-  if ((int)seg_ps_[seg].size() > kTailPieces) return t;
-  t.first = 0;
-  t.f4_per_block = f4_per_block;
-  t.rule = rule_;
-  for (int p : seg_ps_[seg]) {
-    int64_t lo = 0, n = 0;
-    int host = -1;
-    peer_->shard(p, lo, n, host);
-    UpdPiece q;
-    q.w = peer_->params() + lo;
-    q.g = peer_->grads() + lo;
-    q.m = ips_[p].m;
-    q.v = ips_[p].v;
-    q.n = n;
-    q.step = lr_t_[p];
-    t.add_piece(q);
-  }
-  t.finish();
-  return t;
-}
-
-void AsyncRunner::step_inline(const float* x, const int64_t* labels, int B, hipStream_t st) {
+void AsyncRunner::step_inline(const MicroBatch& mb) {
   ++epoch_;
+  upd_launches_ = eng_->update_launches = 0;
   // one Adam step of each PS's own counter per push (TF1: lr_t = lr sqrt(1 - b2^t) / (1 - b1^t))
   for (size_t p = 0; p < ips_.size(); ++p) {
     const int64_t t = ++ips_[p].t;
     lr_t_[p] = adam_step_size(lr_, b1_, b2_, t);
     if (keep_prov_) prov_.push_back({(int64_t)rank_, (int64_t)p, (int64_t)epoch_, t});
   }
-  {
-    TraceRange r("ddl.fwd");
-    eng_->forward(x, B, nullptr, true, st, /*defer_fc2=*/true);
-  }
-  auto apply_now = [&](int seg) {  // a segment whose shards do not fit one tail
-    for (int p : seg_ps_[seg]) {
-      int64_t lo = 0, n = 0;
-      int host = -1;
-      peer_->shard(p, lo, n, host);
-      launch_update(rule_, lr_t_[p], UpdSpan{peer_->params() + lo, ips_[p].m, ips_[p].v},
-                    peer_->grads() + lo, n, st);
-    }
-  };
-  if (clip_.on() || accum_.on()) {
+  const LocalUpdates u{&plan_, rule_, lr_, lr_t_.data(), peer_->params(), peer_->grads()};
+  run_forward(*eng_, mb);
+  if (stage_.whole()) {
     // the norm (and the mean over the micro-batches) needs the whole backward: no tails; finish
     // the accumulation, clip, then every segment's applies in segment order (the push order of
     // the plain step)
-    for (int s = 0; s < kSegments; ++s) {
-      TraceRange r("ddl.bwd");
-      eng_->backward_segment(s, x, labels, B, nullptr, st);
-      eng_->flush_tail(st);
-    }
-    if (accum_.on()) accum_.finish(const_cast<float*>(peer_->grads()), st);
-    if (clip_.on()) clip_.launch(const_cast<float*>(peer_->grads()), st);
-    for (int s = 0; s < kSegments; ++s) apply_now(s);
+    run_whole_backward(*eng_, mb);
+    stage_.finish(grads(), mb.st);
+    for (const auto& sp : plan_.seg) upd_launches_ += launch_piece_updates(u, sp, mb.st);
     return;
   }
-  for (int s = 0; s < kSegments; ++s) {
-    TraceRange r("ddl.bwd");
-    if (s > 0 && !seg_ps_[s - 1].empty()) {
-      UpdTail t = inline_tail(s - 1, kTailF4Default);
-      if (t.npieces) eng_->tail = t;
-      else apply_now(s - 1);
-    }
-    if (s == kSegments - 1 && !seg_ps_[s].empty()) {
-      // one pass per tail block: on the step's critical path the update wants width
-      UpdTail t = inline_tail(s, kTailF4PerBlock);
-      if (t.npieces) eng_->final_upd = t;
-    }
-    eng_->backward_segment(s, x, labels, B, nullptr, st);
-    eng_->flush_tail(st);
-  }
-  if (!seg_ps_[kSegments - 1].empty() &&
-      (eng_->final_upd.npieces > 0 || (int)seg_ps_[kSegments - 1].size() > kTailPieces)) {
-    eng_->final_upd = UpdTail();  // not taken by conv1's launch: a launch of its own
-    apply_now(kSegments - 1);
-  }
+  // a segment whose shards do not fit one tail is applied by launches of its own
+  RidePolicy pol{{}, 0, kTailF4Default, true};
+  for (int s = 0; s < kSegments; ++s) pol.rides[s] = plan_.fits(s);
+  upd_launches_ += run_riding_backward(*eng_, mb, u, pol);
 }
 
 void AsyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t seed,
                        hipStream_t st, double timeout_s) {
   TraceRange step_range("ddl.async.step");
-  accum_.expect(true);
+  stage_.accum.expect(true);
+  const MicroBatch mb{x, labels, B, st, kBwdRange};
   if (inline_) {
     eng_->seed_value = seed;
     last_st_ = st;
     stepped_ = true;
-    step_inline(x, labels, B, st);
+    step_inline(mb);
     return;
   }
   // (1) the previous round's parameters are in place before the forward: the gate enqueued at
@@ -244,37 +204,21 @@ void AsyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t se
   wait_params(timeout_s);
   ++epoch_;
   eng_->seed_value = seed;
-  {
-    TraceRange r("ddl.fwd");
-    eng_->forward(x, B, nullptr, true, st, /*defer_fc2=*/true);  // backward_segment(0) follows
-  }
-  // the gate may only sit on a stream that is not high priority (queried once per stream: a
-  // runtime call at the end of the step would sit in the window where this process's service
-  // thread launches the round's last apply)
-  if (!safe_checked_ || st != safe_stream_) {
-    int lo = 0, hi = 0, pr = 0;  // (the null stream is a normal-priority stream)
-    safe_ = hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess &&
-            (st == nullptr || hipStreamGetPriority(st, &pr) == hipSuccess) && hi != lo &&
-            pr != hi;
-    safe_stream_ = st;
-    safe_checked_ = true;
-  }
-  const bool gate = gate_ && safe_;
+  run_forward(*eng_, mb);
+  // the gate may only sit on a stream that is not high priority, as the service stream is
+  // (queried once per stream: a runtime call at the end of the step would sit in the window where
+  // this process's service thread launches the round's last apply)
+  const bool gate = gate_place_.safe(st, nullptr) && gate_;
   int last = kSegments - 1;
   while (last > 0 && seg_ps_[last].empty()) --last;
   gated_ = 0;
-  const bool clip = clip_.on() || accum_.on();
+  const bool clip = stage_.whole();
   if (clip) {
     // a clipped (or accumulated) round: the whole backward with no push tails, the mean over the
     // micro-batches, the clip, then the pushes below in segment order (push kernels of their
     // own; the last carries the gate)
-    for (int s = 0; s < kSegments; ++s) {
-      TraceRange r("ddl.bwd");
-      eng_->backward_segment(s, x, labels, B, nullptr, st);
-    }
-    eng_->flush_tail(st);
-    if (accum_.on()) accum_.finish(const_cast<float*>(peer_->grads()), st);
-    if (clip_.on()) clip_.launch(const_cast<float*>(peer_->grads()), st);
+    run_whole_backward(*eng_, mb);
+    stage_.finish(grads(), st);
   }
   for (int s = 0; s < kSegments; ++s) {
     if (!clip) {
@@ -311,7 +255,7 @@ void AsyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t se
 void AsyncRunner::accumulate(const float* x, const int64_t* labels, int B, uint32_t seed,
                              hipStream_t st, double timeout_s) {
   TraceRange step_range("ddl.async.accumulate");
-  accum_.expect(false);
+  stage_.accum.expect(false);
   if (inline_) {
     last_st_ = st;
     stepped_ = true;
@@ -319,16 +263,10 @@ void AsyncRunner::accumulate(const float* x, const int64_t* labels, int B, uint3
     wait_params(timeout_s);
   }
   eng_->seed_value = seed;
-  {
-    TraceRange r("ddl.fwd");
-    eng_->forward(x, B, nullptr, true, st, /*defer_fc2=*/true);
-  }
-  for (int s = 0; s < kSegments; ++s) {
-    TraceRange r("ddl.bwd");
-    eng_->backward_segment(s, x, labels, B, nullptr, st);
-  }
-  eng_->flush_tail(st);
-  accum_.accumulate(const_cast<float*>(peer_->grads()), st);
+  const MicroBatch mb{x, labels, B, st, kBwdRange};
+  run_forward(*eng_, mb);
+  run_whole_backward(*eng_, mb);
+  stage_.accum.accumulate(grads(), st);
 }
 
 void AsyncRunner::finish(double timeout_s) {

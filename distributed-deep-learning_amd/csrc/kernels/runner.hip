@@ -64,6 +64,79 @@ __global__ void __launch_bounds__(64) ready_gate_kernel(const uint32_t* flag, ui
   }
 }
 
+// ---- shared with the asynchronous runner (async_runner.hip) -------------------------------------
+void run_forward(Engine& eng, const MicroBatch& mb) {
+  TraceRange r("ddl.fwd");
+  // (dropout seed by kernel argument, Engine::seed_value: no seed-upload kernel, no seed word)
+  eng.forward(mb.x, mb.B, nullptr, true, mb.st, /*defer_fc2=*/true);  // backward_segment(0) follows
+}
+
+void run_whole_backward(Engine& eng, const MicroBatch& mb) {
+  for (int s = 0; s < kPlanSegments; ++s) {
+    TraceRange r(mb.bwd_range[s]);
+    eng.backward_segment(s, mb.x, mb.labels, mb.B, nullptr, mb.st);
+  }
+  eng.flush_tail(mb.st);  // (no-op with nothing pending)
+}
+
+int launch_piece_updates(const LocalUpdates& u, const std::vector<PlanPiece>& pieces,
+                         hipStream_t st) {
+  int launches = 0;
+  for (const auto& p : pieces) {
+    const UpdSpan span{u.w + p.lo, p.m + p.state_off, p.v ? p.v + p.state_off : nullptr};
+    launch_update(u.rule, u.step(p), span, u.g + p.lo, p.n(), st, u.max_grid);
+    launches += p.n() > 0;
+  }
+  return launches;
+}
+
+// `pieces` under u's rule as one optimizer tail (at most kTailPieces of them).  Momentum: v stays
+// null and is never formed.
+static UpdTail tail_of(const LocalUpdates& u, const std::vector<PlanPiece>& pieces, int first,
+                       int f4_per_block) {
+  UpdTail t;
+  t.rule = u.rule;
+  t.first = first;
+  t.f4_per_block = f4_per_block;
+  for (const auto& p : pieces) {
+    UpdPiece q;
+    q.w = u.w + p.lo;
+    q.g = u.g + p.lo;
+    q.m = p.m + p.state_off;
+    q.v = u.rule.kind == kUpdMomentum ? nullptr : p.v + p.state_off;
+    q.n = p.n();
+    q.step = u.step(p);
+    t.add_piece(q);
+  }
+  t.finish();
+  return t;
+}
+
+int run_riding_backward(Engine& eng, const MicroBatch& mb, const LocalUpdates& u,
+                        const RidePolicy& pol) {
+  const auto* seg = u.plan->seg;
+  const int last = kPlanSegments - 1;
+  int launches = 0;
+  for (int s = 0; s < kPlanSegments; ++s) {
+    TraceRange r(mb.bwd_range[s]);
+    if (s > 0 && !seg[s - 1].empty()) {
+      if (pol.rides[s - 1]) eng.tail = tail_of(u, seg[s - 1], pol.first, pol.f4_per_block);
+      else launches += launch_piece_updates(u, seg[s - 1], mb.st);
+    }
+    // one pass per tail block (2 float4 per lane): on the step's critical path the update wants
+    // width, not the long blocks that hide beside a dual launch's GEMM blocks
+    if (s == last && pol.final_in_reduce && pol.rides[s] && !seg[s].empty())
+      eng.final_upd = tail_of(u, seg[s], pol.first, kTailF4PerBlock);
+    eng.backward_segment(s, mb.x, mb.labels, mb.B, nullptr, mb.st);
+    eng.flush_tail(mb.st);
+  }
+  const bool offered = pol.final_in_reduce && pol.rides[last];
+  if (seg[last].empty() || (offered && eng.final_upd.npieces == 0)) return launches;  // taken
+  eng.final_upd = UpdTail();  // not taken by conv1's launch: launches of its own
+  TraceRange r("ddl.update.last_segment");
+  return launches + launch_piece_updates(u, seg[last], mb.st);
+}
+
 SyncRunner::SyncRunner(Engine* eng, float* params, float* grads, int world, int rank)
     : eng_(eng), w_(params), g_(grads), world_(world), rank_(rank) {
   int lo = 0, hi = 0;
@@ -208,74 +281,15 @@ void SyncRunner::set_units(const std::vector<RunnerUnit>& units) {
     if ((units_[i].kind == RunnerUnit::XGMI || units_[i].kind == RunnerUnit::XGMI_REPL) &&
         (last_xgmi_ < 0 || units_[i].seg >= units_[last_xgmi_].seg))
       last_xgmi_ = (int)i;
-  // W = 1 (every unit LOCAL): one stream.  Ranges adjacent in both the parameter buffer and
-  // the PS state merge; per segment they become the optimizer tail of the next segment's dual
-  // launch (tail.h), else all of them one coalesced launch at the end of the step.  Same
-  // result either way: no backward GEMM reads a tensor after its update.
-  merged_.clear();
-  for (auto& sp : seg_pieces_) sp.clear();
-  tail_ok_ = false;
+  // W = 1 (every unit LOCAL): one stream, the updates planned by update_plan.h
+  plan_ = UpdatePlan();
   all_local_ = true;
   for (const auto& u : units_) all_local_ &= (u.kind == RunnerUnit::LOCAL);
   if (!all_local_) return;
-  auto coalesce = [](std::vector<Piece>& v) {
-    std::sort(v.begin(), v.end(), [](const Piece& a, const Piece& b) { return a.r.lo < b.r.lo; });
-    std::vector<Piece> out;
-    for (const auto& p : v) {
-      if (!out.empty()) {
-        Piece& q = out.back();
-        if (q.r.hi == p.r.lo && q.ps == p.ps && q.m == p.m && q.v == p.v &&
-            q.r.state_off + (q.r.hi - q.r.lo) == p.r.state_off) {
-          q.r.hi = p.r.hi;
-          continue;
-        }
-      }
-      out.push_back(p);
-    }
-    v.swap(out);
-  };
   for (const auto& u : units_)
-    for (const auto& r : u.ranges) {
-      merged_.push_back({r, u.ps, u.m, u.v});
-      seg_pieces_[u.seg].push_back({r, u.ps, u.m, u.v});
-    }
-  coalesce(merged_);
-  // tail_ok_: the shape fits for the momentum rule (w, g, m); tail_v_ok_: and every piece has a
-  // vector-shaped v, which the Adam rule needs.  Kept apart so that step() decides by the rule at
-  // that time, whichever of set_optimizer / set_units came first.
-  tail_ok_ = tail_v_ok_ = true;
-  auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  for (auto& sp : seg_pieces_) {
-    coalesce(sp);
-    tail_ok_ &= sp.size() <= (size_t)kTailPieces;
-    for (const auto& p : sp) {
-      tail_ok_ &= p.m && (p.r.hi - p.r.lo) % 4 == 0 && a16(w_ + p.r.lo) && a16(g_ + p.r.lo) &&
-                  a16(p.m + p.r.state_off);
-      tail_v_ok_ &= p.v && a16(p.v + p.r.state_off);
-    }
-  }
-}
-
-// Segment `seg`'s update under the current rule as the optimizer tail of the engine's next dual
-// launch.  Momentum: the step size is lr_, as in update(), and v stays null.
-void SyncRunner::set_tail(int seg, const float* lr_t, int f4_per_block) {
-  UpdTail t;
-  const bool mom = rule_.kind == kUpdMomentum;
-  t.rule = rule_;
-  t.first = tail_first_;
-  t.f4_per_block = f4_per_block > 0 ? f4_per_block : tail_f4_;
-  for (const auto& p : seg_pieces_[seg]) {
-    UpdPiece q;
-    q.w = w_ + p.r.lo;
-    q.g = g_ + p.r.lo;
-    q.m = p.m + p.r.state_off;
-    q.v = mom ? nullptr : p.v + p.r.state_off;
-    q.n = p.r.hi - p.r.lo;
-    q.step = step_of(lr_t[p.ps]);
-    t.add_piece(q);  // (tail_ok_: at most kTailPieces per segment)
-  }
-  t.finish();
-  eng_->tail = t;
+    for (const auto& r : u.ranges)
+      plan_.add(u.seg, PlanPiece{r.lo, r.hi, r.state_off, u.ps, u.m, u.v});
+  plan_.finish(reinterpret_cast<uintptr_t>(w_), reinterpret_cast<uintptr_t>(g_));
 }
 
 void SyncRunner::set_optimizer(int kind, float lr, float b1, float b2, float eps, float mu,
@@ -384,68 +398,35 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
   if (closed_) throw std::runtime_error("sync runner: step() after close()");
   TraceRange step_range("ddl.step");
   upd_launches_ = eng_->update_launches = 0;  // (host counters: update_launches())
-  accum_.expect(true);
-  // (an accumulated step's final micro-batch runs as a clipped step does)
-  const bool whole = clip_.on() || accum_.on();
+  stage_.accum.expect(true);
+  const bool whole = stage_.whole();
   if (whole)
     for (const auto& u : units_)
       if (u.seg != kSegments - 1)
         throw std::invalid_argument("sync runner: a clipped step needs every unit on the last segment");
   eng_->seed_value = seed_value;  // dropout seed by kernel argument: no seed-upload kernel
   const uint32_t* seed = nullptr;
+  const MicroBatch mb{x, labels, B, st, kBwdRange};
   // Cross-queue dependencies (event record -> stream wait) cost tens of microseconds of GPU
   // idle each on this stack (measured), so LOCAL updates go straight onto the compute
   // stream in order; only units with collectives use the comm stream, which then overlaps
   // the remaining backward segments.
-  {
-    TraceRange r("ddl.fwd");
-    eng_->forward(x, B, seed, true, st, /*defer_fc2=*/true);  // backward_segment(0) follows
-  }
-  // (Adam needs every piece's v; momentum / SGD have none and form none)
-  if (all_local_ && local_on_main_ && use_tail_ && tail_ok_ &&
-      (rule_.kind == kUpdMomentum || tail_v_ok_) &&
-      coef_ == 1.f && !whole) {
-    // segment s-1's update rides in segment s's dual launch (flushed as a launch of its own
-    // if the segment had no dual launch to take it); the last segment's follows the backward
-    for (int s = 0; s < kSegments; ++s) {
-      TraceRange r(kBwdRange[s]);
-      if (s > 0 && !seg_pieces_[s - 1].empty()) set_tail(s - 1, lr_t);
-      // the last segment's own update rides in its final launch when the engine can take it
-      // (conv1's weight-gradient reduce: engine_impl.h dual_then_b)
-      if (s == kSegments - 1 && final_in_reduce_ && !seg_pieces_[s].empty()) {
-        // one pass per tail block (2 float4 per lane): on the step's critical path the update
-        // wants width, not the long blocks that hide beside a dual launch's GEMM blocks
-        const UpdTail keep = eng_->tail;
-        set_tail(s, lr_t, kTailF4PerBlock);
-        eng_->final_upd = eng_->tail;
-        eng_->tail = keep;
-      }
-      eng_->backward_segment(s, x, labels, B, seed, st);
-      eng_->flush_tail(st);
-    }
-    if (eng_->final_upd.npieces == 0 && final_in_reduce_ && !seg_pieces_[kSegments - 1].empty())
-      return;  // taken by the last launch
-    eng_->final_upd = UpdTail();
-    TraceRange r("ddl.update.last_segment");
-    for (const auto& p : seg_pieces_[kSegments - 1])
-      update(span_of(p.r, p.m, p.v), g_ + p.r.lo, p.r.hi - p.r.lo, lr_t[p.ps], st);
-    return;
-  }
+  run_forward(*eng_, mb);
   if (all_local_ && local_on_main_) {
-    for (int s = 0; s < kSegments; ++s) {
-      TraceRange r(kBwdRange[s]);
-      eng_->backward_segment(s, x, labels, B, seed, st);
+    const LocalUpdates u{&plan_, rule_, lr_, lr_t, w_, g_, st == cs_ ? DDL_COMM_ADAM_GRID : 2048};
+    // (Adam needs every piece's v; momentum / SGD have none and form none)
+    if (use_tail_ && plan_.tail_ok && (rule_.kind == kUpdMomentum || plan_.tail_v_ok) &&
+        coef_ == 1.f && !whole) {
+      const RidePolicy all_ride{{true, true, true, true}, tail_first_, tail_f4_, final_in_reduce_};
+      upd_launches_ += run_riding_backward(*eng_, mb, u, all_ride);
+      return;
     }
-    if (accum_.on()) {
-      eng_->flush_tail(st);
-      accum_.finish(g_, st);  // the mean over the K micro-batches, ahead of the clip
-    }
-    if (clip_.on()) clip_.launch(g_, st);
+    run_whole_backward(*eng_, mb);
+    stage_.finish(g_, st);  // the mean over the K micro-batches, then the clip
     TraceRange r("ddl.update");
     if (coef_ != 1.f)
-      for (const auto& p : merged_) scale_grads(g_ + p.r.lo, p.r.hi - p.r.lo, st);
-    for (const auto& p : merged_)
-      update(span_of(p.r, p.m, p.v), g_ + p.r.lo, p.r.hi - p.r.lo, lr_t[p.ps], st);
+      for (const auto& p : plan_.merged) scale_grads(g_ + p.lo, p.n(), st);
+    upd_launches_ += launch_piece_updates(u, plan_.merged, st);
     return;
   }
   // The last segment's gradients complete with the backward, so nothing is left to overlap
@@ -472,7 +453,7 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
     // high priority, so the gate never shares a hardware queue with the kernel it waits for;
     // and it is bounded (error 5).
     const bool flag = ready_flags_ > (s == 0 ? 1 : 0) && !on_main && seg_offstream_[s] &&
-                      s + 1 < kSegments && gate_safe(st);
+                      s + 1 < kSegments && gate_place_.safe(st, cs_);
     // otherwise the comm stream waits for this segment's gradients by an event: bound to the
     // segment's kernel launches themselves (the wait below is issued after the last one) rather
     // than a marker packet behind them
@@ -495,11 +476,10 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
     }
     // every unit is the last segment's (checked above): the worker's own clipped gradient is
     // what every exchange and update below reads
-    if (accum_.on() && s == kSegments - 1) {
-      eng_->flush_tail(st);
-      accum_.finish(g_, st);
+    if (whole && s == kSegments - 1) {
+      eng_->flush_tail(st);  // (nothing pending: no segment before the last handed anything over)
+      stage_.finish(g_, st);
     }
-    if (clip_.on() && s == kSegments - 1) clip_.launch(g_, st);
     TraceRange ex_range(kExRange[s]);
     hipStream_t xs = on_main ? st : cs_;
     bool waited = on_main;
@@ -560,35 +540,14 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
 void SyncRunner::accumulate(const float* x, const int64_t* labels, int B, uint32_t seed_value,
                             hipStream_t st) {
   if (closed_) throw std::runtime_error("sync runner: accumulate() after close()");
-  accum_.expect(false);
+  stage_.accum.expect(false);
   TraceRange step_range("ddl.accumulate");
   upd_launches_ = eng_->update_launches = 0;
   eng_->seed_value = seed_value;
-  {
-    TraceRange r("ddl.fwd");
-    eng_->forward(x, B, nullptr, true, st, /*defer_fc2=*/true);
-  }
-  for (int s = 0; s < kSegments; ++s) {
-    TraceRange r(kBwdRange[s]);
-    eng_->backward_segment(s, x, labels, B, nullptr, st);
-  }
-  eng_->flush_tail(st);
-  accum_.accumulate(g_, st);
-}
-
-// The READY gate waits on the comm stream for a kernel of `st`: only safe when `st` cannot share
-// a hardware queue with the comm stream, i.e. when its priority differs from the comm stream's
-// (HIP pools hardware queues per priority; the comm stream is the greatest priority, or the
-// least with DDL_COMM_PRIORITY=low).  Otherwise the segment falls back to the event hand-off.
-bool SyncRunner::gate_safe(hipStream_t st) {
-  if (gate_checked_ && st == gate_checked_stream_) return gate_checked_ok_;
-  int lo = 0, hi = 0, p = 0, cp = 0;  // (the null stream is a normal-priority stream)
-  gate_checked_ok_ = hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess &&
-                     (st == nullptr || hipStreamGetPriority(st, &p) == hipSuccess) &&
-                     hipStreamGetPriority(cs_, &cp) == hipSuccess && hi != lo && p != cp;
-  gate_checked_stream_ = st;
-  gate_checked_ = true;
-  return gate_checked_ok_;
+  const MicroBatch mb{x, labels, B, st, kBwdRange};
+  run_forward(*eng_, mb);
+  run_whole_backward(*eng_, mb);
+  stage_.accum.accumulate(g_, st);
 }
 
 void SyncRunner::issue_xgmi(const RunnerUnit& u, const float* lr_t, bool final_wait,

@@ -26,10 +26,10 @@
 #include <stdint.h>
 
 #include "update.h"
+#include "update_plan.h"  // kTailPieces
 
 namespace ddl {
 
-constexpr int kTailPieces = 4;
 constexpr int kTailF4PerLane = 2;  // float4 per lane per pass: keeps the tail path under the GEMM paths' VGPRs
 constexpr int kTailF4PerBlock = 64 * kTailF4PerLane;  // one-wave blocks
 // float4 per tail block of a segment's Adam riding beside a dual launch's GEMM blocks (8 passes

@@ -462,6 +462,97 @@ struct HandleBlob {  // what one rank publishes (exchanged as bytes over the def
 
 }  // namespace
 
+// ---- PeerMap: the exported buffers and their mappings (PeerExchange, AsyncPeer) -----------------
+#define MAP_CHECK(x)                                                                    \
+  do {                                                                                  \
+    hipError_t e_ = (x);                                                                \
+    if (e_ != hipSuccess)                                                               \
+      throw std::runtime_error(std::string(tag_) + ": " + #x + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+PeerMap::PeerMap(const char* tag, float* params, int world, int rank, double default_timeout_s)
+    : tag_(tag), params_(params), world_(world), rank_(rank) {
+  const char* t = getenv("DDL_XGMI_TIMEOUT_S");
+  timeout_s = t ? atof(t) : default_timeout_s;  // a healthy wait takes microseconds
+}
+
+void PeerMap::alloc(int64_t inbox_elems, size_t flag_bytes) {
+  MAP_CHECK(hipMalloc(&my_inbox, inbox_elems * sizeof(float)));
+  MAP_CHECK(hipMemset(my_inbox, 0, inbox_elems * sizeof(float)));
+  MAP_CHECK(hipExtMallocWithFlags(reinterpret_cast<void**>(&my_flags), flag_bytes,
+                                  hipDeviceMallocUncached));
+  MAP_CHECK(hipMemset(my_flags, 0, flag_bytes));
+  MAP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&err), 64, hipHostMallocDefault));
+  memset(err, 0, 64);
+}
+
+void PeerMap::unmap_peers() {
+  if (opened) (void)hipDeviceSynchronize();
+  for (int q = 0; q < world_; ++q) {
+    if (q == rank_) continue;
+    for (void*& p : mapped_[q]) {
+      if (p) (void)hipIpcCloseMemHandle(p);
+      p = nullptr;
+    }
+  }
+  opened = false;
+}
+
+void PeerMap::close() {
+  if (my_inbox || my_flags || opened) (void)hipDeviceSynchronize();
+  unmap_peers();
+  if (my_inbox) (void)hipFree(my_inbox);
+  if (my_flags) (void)hipFree(my_flags);
+  if (err) (void)hipHostFree(err);
+  my_inbox = nullptr;
+  my_flags = nullptr;
+  err = nullptr;
+}
+
+std::string PeerMap::handle() const {
+  HandleBlob h;
+  memset(&h, 0, sizeof(h));
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  MAP_CHECK(hipMemGetAddressRange(&base, &size, params_));
+  MAP_CHECK(hipIpcGetMemHandle(&h.params, base));
+  h.params_off = reinterpret_cast<const char*>(params_) - reinterpret_cast<const char*>(base);
+  MAP_CHECK(hipIpcGetMemHandle(&h.inbox, my_inbox));
+  MAP_CHECK(hipIpcGetMemHandle(&h.flags, my_flags));
+  h.world = world_;
+  h.rank = rank_;
+  return std::string(reinterpret_cast<const char*>(&h), sizeof(h));
+}
+
+void PeerMap::open(const std::vector<std::string>& handles) {
+  const std::string tag(tag_);
+  if ((int)handles.size() != world_) throw std::invalid_argument(tag + ": one handle per rank");
+  for (int q = 0; q < world_; ++q) {
+    if (handles[q].size() != sizeof(HandleBlob)) throw std::invalid_argument(tag + ": bad handle");
+    HandleBlob h;
+    memcpy(&h, handles[q].data(), sizeof(h));
+    if (h.world != world_ || h.rank != q) throw std::invalid_argument(tag + ": handle rank");
+    if (q == rank_) {
+      table.params[q] = params_;
+      table.inbox[q] = my_inbox;
+      table.flags[q] = my_flags;
+      continue;
+    }
+    void *p = nullptr, *ib = nullptr, *fl = nullptr;
+    MAP_CHECK(hipIpcOpenMemHandle(&p, h.params, hipIpcMemLazyEnablePeerAccess));
+    mapped_[q][0] = p;
+    MAP_CHECK(hipIpcOpenMemHandle(&ib, h.inbox, hipIpcMemLazyEnablePeerAccess));
+    mapped_[q][1] = ib;
+    MAP_CHECK(hipIpcOpenMemHandle(&fl, h.flags, hipIpcMemLazyEnablePeerAccess));
+    mapped_[q][2] = fl;
+    table.params[q] = reinterpret_cast<float*>(reinterpret_cast<char*>(p) + h.params_off);
+    table.inbox[q] = reinterpret_cast<float*>(ib);
+    table.flags[q] = reinterpret_cast<uint32_t*>(fl);
+  }
+  opened = true;
+}
+#undef MAP_CHECK
+
 static std::vector<XgmiBucketSpec> equal_specs(
     const std::vector<std::pair<int64_t, int64_t>>& buckets) {
   std::vector<XgmiBucketSpec> v;
@@ -482,8 +573,8 @@ PeerExchange::PeerExchange(float* params, const float* grads, int64_t total, int
 PeerExchange::PeerExchange(float* params, const float* grads, int64_t total, int world, int rank,
                            const std::vector<XgmiBucketSpec>& buckets, int max_slices,
                            int repl_bucket)
-    : params_(params), grads_(grads), total_(total), world_(world), rank_(rank),
-      repl_(repl_bucket) {
+    : repl_(repl_bucket), params_(params), grads_(grads), total_(total), world_(world),
+      rank_(rank), map_("xgmi", params, world, rank, 20.0) {
   if (world < 1 || world > kXgmiMaxPeers) throw std::invalid_argument("xgmi: world out of range");
   if (rank < 0 || rank >= world) throw std::invalid_argument("xgmi: rank out of range");
   if (buckets.empty() || (int)buckets.size() > kXgmiMaxBuckets)
@@ -569,93 +660,18 @@ void PeerExchange::init(const std::vector<XgmiBucketSpec>& buckets, int max_slic
     inbox += B.slot * world * (repl ? 2 : 1);  // replicated: two parity slots per source
     bk_.push_back(B);
   }
-  inbox_elems_ = inbox;
-  X_CHECK(hipMalloc(&inbox_, inbox_elems_ * sizeof(float)));
-  X_CHECK(hipMemset(inbox_, 0, inbox_elems_ * sizeof(float)));
   // ARRIVE, DONE and (check mode) checksum words, the replicated bucket's in two parities
-  flag_bytes_ = 4ull * kXgmiMaxBuckets * kXgmiMaxPeers * kXgmiMaxSlices * sizeof(uint32_t);
-  X_CHECK(hipExtMallocWithFlags(reinterpret_cast<void**>(&flags_), flag_bytes_,
-                                hipDeviceMallocUncached));
-  X_CHECK(hipMemset(flags_, 0, flag_bytes_));
-  X_CHECK(hipHostMalloc(reinterpret_cast<void**>(&err_), 64, hipHostMallocDefault));
-  memset(err_, 0, 64);
+  map_.alloc(inbox, 4ull * kXgmiMaxBuckets * kXgmiMaxPeers * kXgmiMaxSlices * sizeof(uint32_t));
   X_CHECK(hipDeviceSynchronize());
-  const char* t = getenv("DDL_XGMI_TIMEOUT_S");
-  timeout_s_ = t ? atof(t) : 20.0;  // a healthy wait takes microseconds
   const char* ck = getenv("DDL_XGMI_CHECK");
   check_ = ck && ck[0] == '1';
 }
 
 PeerExchange::~PeerExchange() { close(); }
 
-void PeerExchange::unmap_peers() {
-  if (opened_ok_) (void)hipDeviceSynchronize();
-  for (int q = 0; q < world_; ++q) {
-    if (q == rank_) continue;
-    for (void*& p : opened_[q]) {
-      if (p) (void)hipIpcCloseMemHandle(p);
-      p = nullptr;
-    }
-  }
-  opened_ok_ = false;
-}
-
-void PeerExchange::close() {
-  if (inbox_ || flags_ || opened_ok_) (void)hipDeviceSynchronize();
-  unmap_peers();
-  if (inbox_) (void)hipFree(inbox_);
-  if (flags_) (void)hipFree(flags_);
-  if (err_) (void)hipHostFree(err_);
-  inbox_ = nullptr;
-  flags_ = nullptr;
-  err_ = nullptr;
-}
-
-std::string PeerExchange::handle() const {
-  HandleBlob h;
-  memset(&h, 0, sizeof(h));
-  hipDeviceptr_t base = nullptr;
-  size_t size = 0;
-  X_CHECK(hipMemGetAddressRange(&base, &size, const_cast<float*>(params_)));
-  X_CHECK(hipIpcGetMemHandle(&h.params, base));
-  h.params_off = reinterpret_cast<const char*>(params_) - reinterpret_cast<const char*>(base);
-  X_CHECK(hipIpcGetMemHandle(&h.inbox, inbox_));
-  X_CHECK(hipIpcGetMemHandle(&h.flags, flags_));
-  h.world = world_;
-  h.rank = rank_;
-  return std::string(reinterpret_cast<const char*>(&h), sizeof(h));
-}
-
-void PeerExchange::open(const std::vector<std::string>& handles) {
-  if ((int)handles.size() != world_) throw std::invalid_argument("xgmi: need one handle per rank");
-  for (int q = 0; q < world_; ++q) {
-    if (handles[q].size() != sizeof(HandleBlob)) throw std::invalid_argument("xgmi: bad handle");
-    HandleBlob h;
-    memcpy(&h, handles[q].data(), sizeof(h));
-    if (h.world != world_ || h.rank != q) throw std::invalid_argument("xgmi: handle rank mismatch");
-    if (q == rank_) {
-      table_.params[q] = params_;
-      table_.inbox[q] = inbox_;
-      table_.flags[q] = flags_;
-      continue;
-    }
-    void *p = nullptr, *ib = nullptr, *fl = nullptr;
-    X_CHECK(hipIpcOpenMemHandle(&p, h.params, hipIpcMemLazyEnablePeerAccess));
-    opened_[q][0] = p;
-    X_CHECK(hipIpcOpenMemHandle(&ib, h.inbox, hipIpcMemLazyEnablePeerAccess));
-    opened_[q][1] = ib;
-    X_CHECK(hipIpcOpenMemHandle(&fl, h.flags, hipIpcMemLazyEnablePeerAccess));
-    opened_[q][2] = fl;
-    table_.params[q] = reinterpret_cast<float*>(reinterpret_cast<char*>(p) + h.params_off);
-    table_.inbox[q] = reinterpret_cast<float*>(ib);
-    table_.flags[q] = reinterpret_cast<uint32_t*>(fl);
-  }
-  opened_ok_ = true;
-}
-
 void PeerExchange::fill(int bucket, uint32_t epoch, const XgmiUpdate& u, bool final_wait,
                         bool gated, XgmiLaunch& a) const {
-  if (!opened_ok_) throw std::runtime_error("xgmi: open() the peer handles first");
+  if (!map_.opened) throw std::runtime_error("xgmi: open() the peer handles first");
   if (bucket < 0 || bucket >= (int)bk_.size()) throw std::invalid_argument("xgmi: bucket index");
   const Bucket& B = bk_[bucket];
   const bool owns = B.owner < 0 || B.owner == rank_;  // runs the update of (part of) the bucket
@@ -681,8 +697,8 @@ void PeerExchange::fill(int bucket, uint32_t epoch, const XgmiUpdate& u, bool fi
   a.rule = u.rule;
   a.step = u.step;
   a.coef = u.coef;
-  a.err = err_;
-  a.timeout_ticks = (long long)(timeout_s_ * 1e8);  // wall_clock64: 100 MHz
+  a.err = map_.err;
+  a.timeout_ticks = map_.timeout_ticks();
   a.check = check_ ? 1 : 0;
   a.repl_bucket = repl_;
   a.gate_err = gated ? gate_err_ : nullptr;
@@ -711,10 +727,10 @@ void PeerExchange::launch(int bucket, uint32_t epoch, const XgmiUpdate& u, bool 
   if (B.owner >= 0) {
     switch (world_) {
 #define X_CASE(N) \
-  case N: DDL_LAUNCH(xgmi_owner_kernel<N>, dim3(B.nslice), dim3(256), 0, st, table_, a); break;
+  case N: DDL_LAUNCH(xgmi_owner_kernel<N>, dim3(B.nslice), dim3(256), 0, st, map_.table, a); break;
       X_CASE(1) X_CASE(2) X_CASE(3) X_CASE(4) X_CASE(5) X_CASE(6) X_CASE(7) X_CASE(8)
 #undef X_CASE
-      default: DDL_LAUNCH(xgmi_owner_kernel<0>, dim3(B.nslice), dim3(256), 0, st, table_, a);
+      default: DDL_LAUNCH(xgmi_owner_kernel<0>, dim3(B.nslice), dim3(256), 0, st, map_.table, a);
     }
     DDL_CHECK_LAUNCH();
     return;
@@ -722,26 +738,22 @@ void PeerExchange::launch(int bucket, uint32_t epoch, const XgmiUpdate& u, bool 
   if (bucket == repl_) {
     switch (world_) {
 #define X_CASE(N) \
-  case N: DDL_LAUNCH(xgmi_repl_kernel<N>, dim3(B.nslice), dim3(256), 0, st, table_, a); break;
+  case N: DDL_LAUNCH(xgmi_repl_kernel<N>, dim3(B.nslice), dim3(256), 0, st, map_.table, a); break;
       X_CASE(2) X_CASE(3) X_CASE(4) X_CASE(5) X_CASE(6) X_CASE(7) X_CASE(8)
 #undef X_CASE
-      default: DDL_LAUNCH(xgmi_repl_kernel<0>, dim3(B.nslice), dim3(256), 0, st, table_, a);
+      default: DDL_LAUNCH(xgmi_repl_kernel<0>, dim3(B.nslice), dim3(256), 0, st, map_.table, a);
     }
     DDL_CHECK_LAUNCH();
     return;
   }
   switch (world_) {
 #define X_CASE(N) \
-  case N: DDL_LAUNCH(xgmi_ps_kernel<N>, dim3(B.nslice), dim3(256), 0, st, table_, a); break;
+  case N: DDL_LAUNCH(xgmi_ps_kernel<N>, dim3(B.nslice), dim3(256), 0, st, map_.table, a); break;
     X_CASE(2) X_CASE(3) X_CASE(4) X_CASE(5) X_CASE(6) X_CASE(7) X_CASE(8)
 #undef X_CASE
-    default: DDL_LAUNCH(xgmi_ps_kernel<0>, dim3(B.nslice), dim3(256), 0, st, table_, a);
+    default: DDL_LAUNCH(xgmi_ps_kernel<0>, dim3(B.nslice), dim3(256), 0, st, map_.table, a);
   }
   DDL_CHECK_LAUNCH();
-}
-
-int PeerExchange::error() const {
-  return err_ ? __atomic_load_n(err_, __ATOMIC_ACQUIRE) : 0;
 }
 
 // ---- the stale-L2 probe of the xGMI self-test (native_exchange.py) ----------------------------

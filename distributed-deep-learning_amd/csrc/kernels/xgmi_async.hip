@@ -277,18 +277,13 @@ __global__ void __launch_bounds__(64) async_gate_kernel(const AsyncTable* __rest
       throw std::runtime_error(std::string("xgmi-async: ") + #x + ": " + hipGetErrorString(e_)); \
   } while (0)
 
-struct HandleBlob {
-  hipIpcMemHandle_t params, inbox, flags;
-  int64_t params_off;
-  int32_t world, rank;
-};
-
 }  // namespace
 
 AsyncPeer::AsyncPeer(float* params, const float* grads, int64_t total, int world, int rank,
                      const std::vector<std::pair<int64_t, int64_t>>& ps_ranges,
                      const std::vector<int>& ps_host, int max_slices)
-    : params_(params), grads_(grads), world_(world), rank_(rank) {
+    : params_(params), grads_(grads), world_(world), rank_(rank),
+      map_("xgmi-async", params, world, rank, 60.0) {
   if (world < 1 || world > kXgmiMaxPeers) throw std::invalid_argument("async xgmi: world");
   if (rank < 0 || rank >= world) throw std::invalid_argument("async xgmi: rank");
   if (ps_ranges.empty() || (int)ps_ranges.size() > kAsyncMaxPs ||
@@ -328,19 +323,10 @@ AsyncPeer::AsyncPeer(float* params, const float* grads, int64_t total, int world
     off[S.host] += S.n * world;
   }
   inbox = off[rank];
-  inbox_elems_ = inbox > 0 ? inbox : 4;
-  X_CHECK(hipMalloc(&inbox_, inbox_elems_ * sizeof(float)));
-  X_CHECK(hipMemset(inbox_, 0, inbox_elems_ * sizeof(float)));
-  const size_t flag_bytes = kAsyncFlagWords * sizeof(uint32_t);  // DONE, then POSTED[worker]
-  X_CHECK(hipExtMallocWithFlags(reinterpret_cast<void**>(&flags_), flag_bytes,
-                                hipDeviceMallocUncached));
-  X_CHECK(hipMemset(flags_, 0, flag_bytes));
-  X_CHECK(hipHostMalloc(reinterpret_cast<void**>(&err_), 64, hipHostMallocDefault));
-  memset(err_, 0, 64);
+  // the flags: DONE, then POSTED[worker]
+  map_.alloc(inbox > 0 ? inbox : 4, kAsyncFlagWords * sizeof(uint32_t));
   X_CHECK(hipMalloc(reinterpret_cast<void**>(&table_dev_), sizeof(AsyncTable)));
   X_CHECK(hipDeviceSynchronize());
-  const char* t = getenv("DDL_XGMI_TIMEOUT_S");
-  timeout_s_ = t ? atof(t) : 60.0;
   const char* el = getenv("DDL_ASYNC_ELIDE_LOCAL");
   table_.grads = grads;
   table_.elide = el ? atoi(el) != 0 : 1;
@@ -348,28 +334,9 @@ AsyncPeer::AsyncPeer(float* params, const float* grads, int64_t total, int world
 
 AsyncPeer::~AsyncPeer() { close(); }
 
-void AsyncPeer::unmap_peers() {
-  if (opened_ok_) (void)hipDeviceSynchronize();
-  for (int q = 0; q < world_; ++q) {
-    if (q == rank_) continue;
-    for (void*& p : opened_[q]) {
-      if (p) (void)hipIpcCloseMemHandle(p);
-      p = nullptr;
-    }
-  }
-  opened_ok_ = false;
-}
-
 void AsyncPeer::close() {
-  if (inbox_ || flags_ || opened_ok_) (void)hipDeviceSynchronize();
-  unmap_peers();
-  if (inbox_) (void)hipFree(inbox_);
-  if (flags_) (void)hipFree(flags_);
-  if (err_) (void)hipHostFree(err_);
+  map_.close();
   if (table_dev_) (void)hipFree(table_dev_);
-  inbox_ = nullptr;
-  flags_ = nullptr;
-  err_ = nullptr;
   table_dev_ = nullptr;
   if (done_host_) {
     (void)hipHostUnregister(done_host_);
@@ -380,47 +347,14 @@ void AsyncPeer::close() {
   posted_host_ = nullptr;
 }
 
-std::string AsyncPeer::handle() const {
-  HandleBlob h;
-  memset(&h, 0, sizeof(h));
-  hipDeviceptr_t base = nullptr;
-  size_t size = 0;
-  X_CHECK(hipMemGetAddressRange(&base, &size, const_cast<float*>(params_)));
-  X_CHECK(hipIpcGetMemHandle(&h.params, base));
-  h.params_off = reinterpret_cast<const char*>(params_) - reinterpret_cast<const char*>(base);
-  X_CHECK(hipIpcGetMemHandle(&h.inbox, inbox_));
-  X_CHECK(hipIpcGetMemHandle(&h.flags, flags_));
-  h.world = world_;
-  h.rank = rank_;
-  return std::string(reinterpret_cast<const char*>(&h), sizeof(h));
-}
-
 void AsyncPeer::open(const std::vector<std::string>& handles) {
-  if ((int)handles.size() != world_) throw std::invalid_argument("async xgmi: one handle per rank");
-  for (int q = 0; q < world_; ++q) {
-    if (handles[q].size() != sizeof(HandleBlob)) throw std::invalid_argument("async xgmi: handle");
-    HandleBlob h;
-    memcpy(&h, handles[q].data(), sizeof(h));
-    if (h.world != world_ || h.rank != q) throw std::invalid_argument("async xgmi: handle rank");
-    if (q == rank_) {
-      table_.params[q] = params_;
-      table_.inbox[q] = inbox_;
-      table_.flags[q] = flags_;
-      continue;
-    }
-    void *p = nullptr, *ib = nullptr, *fl = nullptr;
-    X_CHECK(hipIpcOpenMemHandle(&p, h.params, hipIpcMemLazyEnablePeerAccess));
-    opened_[q][0] = p;
-    X_CHECK(hipIpcOpenMemHandle(&ib, h.inbox, hipIpcMemLazyEnablePeerAccess));
-    opened_[q][1] = ib;
-    X_CHECK(hipIpcOpenMemHandle(&fl, h.flags, hipIpcMemLazyEnablePeerAccess));
-    opened_[q][2] = fl;
-    table_.params[q] = reinterpret_cast<float*>(reinterpret_cast<char*>(p) + h.params_off);
-    table_.inbox[q] = reinterpret_cast<float*>(ib);
-    table_.flags[q] = reinterpret_cast<uint32_t*>(fl);
-  }
+  map_.open(handles);
+  memcpy(table_.params, map_.table.params, sizeof(table_.params));
+  memcpy(table_.inbox, map_.table.inbox, sizeof(table_.inbox));
+  memcpy(table_.flags, map_.table.flags, sizeof(table_.flags));
+  map_.opened = false;  // (until the kernels' copy of the table is in place)
   upload_table();
-  opened_ok_ = true;
+  map_.opened = true;
 }
 
 void AsyncPeer::shard(int p, int64_t& lo, int64_t& n, int& host) const {
@@ -435,7 +369,7 @@ void AsyncPeer::upload_table() {
 }
 
 void AsyncPeer::push_all(uint32_t epoch, float coef, hipStream_t st) {
-  if (!opened_ok_ || !table_.posted)
+  if (!map_.opened || !table_.posted)
     throw std::runtime_error("async xgmi: open(), attach_done() first");
   PushArgs a;
   memset(&a, 0, sizeof(a));
@@ -459,7 +393,7 @@ void AsyncPeer::push_all(uint32_t epoch, float coef, hipStream_t st) {
 
 void AsyncPeer::push_set(const std::vector<int>& ps, uint32_t epoch, float coef, hipStream_t st,
                          bool with_gate) {
-  if (!opened_ok_ || !table_.posted)
+  if (!map_.opened || !table_.posted)
     throw std::runtime_error("async xgmi: open(), attach_done() first");
   if (ps.empty()) return;
   if ((int)ps.size() > kAsyncMaxPs) throw std::invalid_argument("async xgmi: PS list");
@@ -486,8 +420,8 @@ void AsyncPeer::push_set(const std::vector<int>& ps, uint32_t epoch, float coef,
     if (!table_.done) throw std::runtime_error("async xgmi: attach_done() first");
     a.gate = 1;
     a.gate_total = table_.shard[nps_ - 1].slice0 + table_.shard[nps_ - 1].nslice;
-    a.err = err_;
-    a.timeout_ticks = (long long)(timeout_s_ * 1e8);
+    a.err = map_.err;
+    a.timeout_ticks = map_.timeout_ticks();
     ++blk;
   }
   hipLaunchKernelGGL(async_push_kernel, dim3(blk), dim3(256), 0, st, table_dev_, a);
@@ -495,7 +429,7 @@ void AsyncPeer::push_set(const std::vector<int>& ps, uint32_t epoch, float coef,
 }
 
 bool AsyncPeer::push_tail(const std::vector<int>& ps, uint32_t epoch, UpdTail& out) const {
-  if (!opened_ok_ || !table_.posted)
+  if (!map_.opened || !table_.posted)
     throw std::runtime_error("async xgmi: open(), attach_done() first");
   if (ps.empty() || (int)ps.size() > kTailPieces) return false;
   UpdTail t;
@@ -599,7 +533,7 @@ bool AsyncPeer::wait_done(uint32_t epoch, double timeout_s) {
 
 void AsyncPeer::apply(int ps, int worker, uint32_t epoch, const XgmiUpdate& u, float* ps_params,
                       hipStream_t st) {
-  if (!opened_ok_ || !table_.done) throw std::runtime_error("async xgmi: open(), attach_done() first");
+  if (!map_.opened || !table_.done) throw std::runtime_error("async xgmi: open(), attach_done() first");
   if (ps < 0 || ps >= nps_ || table_.shard[ps].host != rank_)
     throw std::invalid_argument("async xgmi: apply on a PS this rank does not host");
   if (worker < 0 || worker >= world_) throw std::invalid_argument("async xgmi: worker");
@@ -623,18 +557,17 @@ void AsyncPeer::apply(int ps, int worker, uint32_t epoch, const XgmiUpdate& u, f
 }
 
 void AsyncPeer::gate(uint32_t epoch, hipStream_t st) {
-  if (!opened_ok_ || !table_.done) throw std::runtime_error("async xgmi: open(), attach_done() first");
+  if (!map_.opened || !table_.done) throw std::runtime_error("async xgmi: open(), attach_done() first");
   GateArgs a;
   a.total = table_.shard[nps_ - 1].slice0 + table_.shard[nps_ - 1].nslice;
   a.epoch = epoch;
-  a.err = err_;
-  a.timeout_ticks = (long long)(timeout_s_ * 1e8);
+  a.err = map_.err;
+  a.timeout_ticks = map_.timeout_ticks();
   a.rank = rank_;
   hipLaunchKernelGGL(async_gate_kernel, dim3(1), dim3(64), 0, st, table_dev_, a);
   DDL_CHECK_LAUNCH();
 }
 
-int AsyncPeer::error() const { return err_ ? __atomic_load_n(err_, __ATOMIC_ACQUIRE) : 0; }
 
 // ---- the PS service loop in C++ -------------------------------------------------------------------
 // Scans the arrival board of this host's PS and enqueues one apply per completed push on one PS

@@ -35,7 +35,7 @@ import torch
 import torch.distributed as dist
 
 from ..ops import native
-from .comm import DistEnv
+from .comm import DistEnv, agree
 from .ps import ParameterServer
 from .sharding import ShardPlan
 
@@ -76,17 +76,6 @@ class AsyncPeerExchange:
         self.hosts = [plan.host_rank(p, W) for p in range(P)]
         ops = native.ops()
 
-        def agree(ok: bool, why: str, what: str) -> None:
-            if W == 1:
-                if not ok:
-                    raise AsyncPeerUnavailable(f"{what} failed: {why}")
-                return
-            votes = [None] * W
-            dist.all_gather_object(votes, (bool(ok), why))
-            bad = [(q, w) for q, (o, w) in enumerate(votes) if not o]
-            if bad:
-                raise AsyncPeerUnavailable(f"{what} failed on ranks {bad}")
-
         peer, mine, why = None, None, ""
         try:
             peer = ops.AsyncPeer(params, grads, W, r, [tuple(map(int, x)) for x in self.ranges],
@@ -94,7 +83,7 @@ class AsyncPeerExchange:
             mine = peer.handle()
         except RuntimeError as e:
             why = str(e)
-        agree(mine is not None, why, "async xGMI buffer export")
+        agree(env, mine is not None, why, "async xGMI buffer export", AsyncPeerUnavailable)
         handles = [mine]
         if W > 1:
             handles = [None] * W
@@ -104,7 +93,7 @@ class AsyncPeerExchange:
             peer.open(handles)
         except RuntimeError as e:
             why = str(e)
-        agree(not why, why, "async xGMI peer mapping")
+        agree(env, not why, why, "async xGMI peer mapping", AsyncPeerUnavailable)
         done_name = f"/{job_id}_xdone"
         why = ""
         try:
@@ -112,15 +101,17 @@ class AsyncPeerExchange:
                 peer.attach_done(done_name, True)
         except RuntimeError as e:
             why = str(e)
-        agree(not why, why, "async xGMI completion counters (create)")
+        agree(env, not why, why, "async xGMI completion counters (create)",
+              AsyncPeerUnavailable)
         try:
             if r != 0:
                 peer.attach_done(done_name, False)
         except RuntimeError as e:
             why = str(e)
-        agree(not why, why, "async xGMI completion counters (attach)")
+        agree(env, not why, why, "async xGMI completion counters (attach)",
+              AsyncPeerUnavailable)
         self.peer = peer
-        self._selftest(agree)
+        self._selftest()
 
         if W > 1:
             dist.barrier()
@@ -186,7 +177,7 @@ class AsyncPeerExchange:
                 torch.cuda.synchronize(self.params.device)
 
     # -- set-up check ------------------------------------------------------------------------------
-    def _selftest(self, agree) -> None:
+    def _selftest(self) -> None:
         """Round 1 with the self-test update (PS shard := pushed gradient): every worker must
         get back exactly what it pushed, from every PS."""
         W, r = self.env.world, self.env.rank
@@ -220,7 +211,7 @@ class AsyncPeerExchange:
         self.params.copy_(saved)
         self.grads.zero_()
         torch.cuda.synchronize(dev)
-        agree(ok, why, "async xGMI self-test")
+        agree(self.env, ok, why, "async xGMI self-test", AsyncPeerUnavailable)
         self.epoch = 1                                   # worker rounds done
 
     # -- PS service thread -------------------------------------------------------------------------

@@ -55,6 +55,21 @@ class DistEnv:
         return self.world > 1
 
 
+def agree(env: DistEnv, ok: bool, why: str, what: str, exc: type) -> None:
+    """One go/no-go vote over the default process group: every rank raises ``exc`` when any rank
+    says no, so all ranks fall back together instead of leaving the others stuck in a collective.
+    With one worker there is nobody to ask."""
+    if env.world == 1:
+        if not ok:
+            raise exc(f"{what} failed: {why}")
+        return
+    votes = [None] * env.world
+    dist.all_gather_object(votes, (bool(ok), why))
+    bad = [(r, w) for r, (o, w) in enumerate(votes) if not o]
+    if bad:
+        raise exc(f"{what} failed on ranks {bad}")
+
+
 def share_gpu_queue_cap(local_world: int) -> Optional[str]:
     """Ranks sharing one GPU (the one-box rehearsal): one hardware queue per process.
 

@@ -38,7 +38,7 @@ import torch.distributed as dist
 
 from ..ops import native
 from ..ops.adam import adam_coeffs
-from .comm import DistEnv, SyncExchange
+from .comm import DistEnv, SyncExchange, agree
 from .ps import ParameterServer
 from .sharding import ShardPlan
 
@@ -197,15 +197,8 @@ class NativeSyncExchange(SyncExchange):
         """Every go/no-go decision is voted on over the default process group BEFORE any rank
         enters a blocking RCCL call, so a rank that cannot use the native path makes all ranks
         fall back together instead of leaving the others stuck in ``ncclCommInitRank``."""
-        def agree(ok: bool, why: str, what: str) -> None:
-            votes = [None] * env.world
-            dist.all_gather_object(votes, (bool(ok), why))
-            bad = [(r, w) for r, (o, w) in enumerate(votes) if not o]
-            if bad:
-                raise NativeUnavailable(f"{what} failed on ranks {bad}")
-
         why = ops.SyncRunner.probe()
-        agree(not why, why, "RCCL symbol probe")
+        agree(env, not why, why, "RCCL symbol probe", NativeUnavailable)
         ids = [None, ""]
         if env.rank == 0:
             try:
@@ -217,7 +210,7 @@ class NativeSyncExchange(SyncExchange):
             raise NativeUnavailable(f"ncclGetUniqueId failed on rank 0: {ids[1]}")
         self.runner.init_comm(ids[0])
         ok, why = self.runner.selftest()
-        agree(ok, why, "RCCL self-test")
+        agree(env, ok, why, "RCCL self-test", NativeUnavailable)
 
     def _owner_specs(self):
         """One xGMI owner bucket per exchange unit of a plan without one equal chunk per rank:
@@ -242,17 +235,6 @@ class NativeSyncExchange(SyncExchange):
         (rank + 1) * (i % 13 + 1), one exchange with w := sum of g must give
         W (W + 1) / 2 * (i % 13 + 1) everywhere (exact in fp32).  Every stage is voted on, so
         a failure anywhere makes all ranks fall back together."""
-        def agree(ok: bool, why: str, what: str) -> None:
-            if env.world == 1:
-                if not ok:
-                    raise NativeUnavailable(f"{what} failed: {why}")
-                return
-            votes = [None] * env.world
-            dist.all_gather_object(votes, (bool(ok), why))
-            bad = [(r, w) for r, (o, w) in enumerate(votes) if not o]
-            if bad:
-                raise NativeUnavailable(f"{what} failed on ranks {bad}")
-
         peer, why = None, ""
         try:
             # at most this many workgroups per bucket kernel (>= 1024 elements each;
@@ -272,7 +254,7 @@ class NativeSyncExchange(SyncExchange):
             mine = peer.handle()
         except (RuntimeError, ValueError) as e:  # (pybind11: invalid_argument -> ValueError)
             mine, why = None, str(e)
-        agree(mine is not None, why, "xGMI buffer export")
+        agree(env, mine is not None, why, "xGMI buffer export", NativeUnavailable)
         handles = [mine]
         if env.world > 1:
             handles = [None] * env.world
@@ -282,7 +264,7 @@ class NativeSyncExchange(SyncExchange):
             why = ""
         except (RuntimeError, ValueError) as e:
             why = str(e)
-        agree(not why, why, "xGMI peer mapping")
+        agree(env, not why, why, "xGMI peer mapping", NativeUnavailable)
         self.runner.set_peer(peer)
         self.peer = peer
         saved = params.clone()
@@ -322,7 +304,7 @@ class NativeSyncExchange(SyncExchange):
         params.copy_(saved)
         grads.zero_()
         torch.cuda.synchronize(params.device)
-        agree(ok, why, "xGMI self-test")
+        agree(env, ok, why, "xGMI self-test", NativeUnavailable)
 
     def step(self, x: torch.Tensor, labels: torch.Tensor, keep_prob: float, seed: int) -> None:
         """One synchronous global step: every hosted PS advances its step counter (one

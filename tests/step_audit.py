@@ -7,9 +7,11 @@ tests/test_step_audit_cpu.py runs the same functions without a GPU: that they no
 updated too early, that the pool-code rule holds for the data used, and that the update yardstick
 is the parameter server's.
 
-`expected_update_launches` is the host logic of `SyncRunner::set_units` / `SyncRunner::step`
-(csrc/kernels/runner.hip) and of the engine's last launch (engine_impl.h dual_then_b) written down
-once more, from which the GPU test's table of `update_launches()` is derived.
+`coalesced` is the planner of csrc/kernels/update_plan.h written down once more (the CPU test runs
+the real one beside it), and `expected_update_launches` the host logic of `SyncRunner::step`,
+`AsyncRunner::step_inline` and their shared `run_riding_backward` (csrc/kernels/runner.hip) and of
+the engine's last launch (engine_impl.h dual_then_b); the GPU test's table of `update_launches()`
+is derived from them.
 """
 import torch
 
@@ -168,10 +170,41 @@ def chained_step(P, x, labels, seed, dtype=torch.float64):
 
 
 # ---- which launch carries which update ---------------------------------------------------------
+def unit_pieces(units, seg_sets, overlap=True):
+    """What SyncRunner::set_units hands the planner at W = 1: per backward segment the
+    (lo, hi, ps, state_off) ranges of its units, in unit order."""
+    segs = [[] for _ in seg_sets]
+    for u in units:
+        s = len(seg_sets) - 1 if not overlap else max(
+            next(i for i, ss in enumerate(seg_sets) if t in ss) for t in u.tensors)
+        offs = u.state_offs or [0] * len(u.ranges)
+        segs[s] += [(lo, hi, u.ps, off) for (lo, hi), off in zip(u.ranges, offs)]
+    return segs
+
+
+def inline_pieces(plan, seg_sets):
+    """What AsyncRunner::set_inline hands the planner: each PS's one range with that PS's own
+    state, in the last backward segment any of its tensors completes in (async_xgmi.py
+    attach_runner)."""
+    from ddl_amd.models.layout import TENSORS
+    off = plan.tensor_offsets
+    segs = [[] for _ in seg_sets]
+    for p in range(plan.num_ps):
+        (lo, hi), = plan.ps_segments(p)
+        ts = [t.index for t in TENSORS if off[t.index] < hi and off[t.index] + t.numel > lo]
+        s = max(next(i for i, ss in enumerate(seg_sets) if t in ss) for t in ts)
+        segs[s].append((lo, hi, p, 0))
+    return segs
+
+
 def segment_pieces(units, seg_sets, overlap=True):
-    """SyncRunner::set_units at W = 1: per backward segment the (lo, hi, ps, state_off) ranges of
-    its units, coalesced where adjacent in the buffer and in one PS's state; and all of them
-    coalesced (`merged_`)."""
+    """SyncRunner::set_units at W = 1: the coalesced pieces of the units' ranges."""
+    return coalesced(unit_pieces(units, seg_sets, overlap))
+
+
+def coalesced(segs):
+    """UpdatePlan::finish (csrc/kernels/update_plan.h): each segment's pieces coalesced where
+    adjacent in the buffer and in one PS's state; and all of them coalesced (`merged`)."""
     def coalesce(v):
         out = []
         for lo, hi, ps, off in sorted(v):
@@ -182,12 +215,6 @@ def segment_pieces(units, seg_sets, overlap=True):
                 out.append((lo, hi, ps, off))
         return out
 
-    segs = [[] for _ in seg_sets]
-    for u in units:
-        s = len(seg_sets) - 1 if not overlap else max(
-            next(i for i, ss in enumerate(seg_sets) if t in ss) for t in u.tensors)
-        offs = u.state_offs or [0] * len(u.ranges)
-        segs[s] += [(lo, hi, u.ps, off) for (lo, hi), off in zip(u.ranges, offs)]
     return [coalesce(s) for s in segs], coalesce([p for s in segs for p in s])
 
 
@@ -212,20 +239,21 @@ def final_split_conv12_ok(pieces, offsets):
 
 
 def expected_update_launches(seg_pieces, merged, offsets, use_tail=True, final_in_reduce=True,
-                             dual=True, conv1_direct=True):
-    """Stand-alone optimizer launches of one W = 1 step (SyncRunner::update_launches), by reading
-    SyncRunner::step.  Every plan buffer keeps tensors and PS chunks on 64-element boundaries, so
-    the alignment and length conditions of tail_ok_ always hold here; what decides is the piece
-    count."""
-    tail_ok = all(len(sp) <= TAIL_PIECES for sp in seg_pieces)
-    if not (use_tail and tail_ok):
+                             dual=True, conv1_direct=True, per_segment=False):
+    """Stand-alone optimizer launches of one W = 1 step (update_launches() of either runner), by
+    reading SyncRunner::step, AsyncRunner::step_inline and run_riding_backward (runner.hip).  Every
+    plan buffer keeps tensors and PS chunks on 64-element boundaries, so the alignment and length
+    conditions of tail_ok always hold here; what decides is the piece count.  per_segment: the
+    in-line runner's policy, a segment with more than TAIL_PIECES pieces is launched piece by
+    piece and the others still ride; otherwise one such segment sends every update after the
+    backward (SyncRunner)."""
+    rides = [len(sp) <= TAIL_PIECES for sp in seg_pieces]
+    if not per_segment and not (use_tail and all(rides)):
         return len(merged)           # the coalesced launches after the backward
-    n = 0
-    if not dual:                     # run_back_to_back flushes the pending tail, a launch per piece
-        n += sum(len(sp) for sp in seg_pieces[:-1])
+    # (without dual launches run_back_to_back flushes the pending tail, a launch per piece)
+    n = sum(len(sp) for sp, r in zip(seg_pieces[:-1], rides) if not (r and dual))
     last = seg_pieces[-1]
-    if conv1_direct:
-        taken = final_in_reduce and dual and final_split_conv12_ok(last, offsets)
-    else:                            # final_split + launch_reduce_tail: conv1's spans cut out
-        taken = final_in_reduce and dual
+    taken = rides[-1] and final_in_reduce and dual
+    if conv1_direct:                 # (else final_split + launch_reduce_tail: conv1's spans cut out)
+        taken = taken and final_split_conv12_ok(last, offsets)
     return n + (0 if taken else len(last))

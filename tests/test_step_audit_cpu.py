@@ -6,7 +6,8 @@ without a GPU on the audit's parameters, learning rate and data:
 * the pool-code rule passes on the fp32 CPU chain, which differs from the fp64 codes nowhere;
 * the update yardstick (exchange_reference.rule_step) is parallel/ps.py's pure-torch branch at
   this learning rate and these gradients;
-* the table of `update_launches()` agrees with the runner's host logic on every plan.
+* the tables of `update_launches()` agree with the runners' host logic on every plan, and that
+  logic's planner half with the real planner (update_plan.h) run as a host program.
 """
 import pytest
 import torch
@@ -22,7 +23,7 @@ from ddl_amd.parallel.comm import DistEnv, SyncExchange
 from ddl_amd.parallel.ps import ParameterServer
 from ddl_amd.parallel.roles import resolve_num_ps
 from ddl_amd.config import TrainConfig
-from ddl_amd.parallel.sharding import make_plan
+from ddl_amd.parallel.sharding import async_groups, make_plan
 from oracle_common import BATCHES, make_real_params
 
 EPS32 = float(torch.finfo(torch.float32).eps)
@@ -173,7 +174,10 @@ def test_update_yardstick_matches_parameter_server(P, chain33, optimizer, kind, 
     assert not torch.equal(w, w0)
 
 
-def cell_pieces(kw):
+SEG_SETS = [set(s) for s in HIP_SEGMENTS]
+
+
+def cell_units(kw):
     cfg = TrainConfig(mode="sync", **kw)
     n = resolve_num_ps(cfg, 1)
     plan = make_plan(cfg.shard, n, buckets=HIP_SEGMENTS if cfg.shard == "flat" else None)
@@ -182,12 +186,80 @@ def cell_pieces(kw):
     ex = SyncExchange(plan, DistEnv(0, 1, 0, torch.device("cpu")), z, z.clone(), HIP_SEGMENTS,
                       servers)
     assert all(u.kind == "local" for u in ex.units)
-    return plan, A.segment_pieces(ex.units, [set(s) for s in HIP_SEGMENTS])
+    return plan, ex.units
+
+
+def cell_pieces(kw):
+    plan, units = cell_units(kw)
+    return plan, A.segment_pieces(units, SEG_SETS)
+
+
+def inline_plan(num_ps):
+    """The in-line audit's plan (parallel/roles.py, async mode, flat)."""
+    return make_plan("flat", num_ps, buckets=async_groups(HIP_SEGMENTS), segment_aligned=True)
+
+
+def test_planner_agrees_with_its_python_twin(tmp_path):
+    """csrc/kernels/update_plan.h, the planner both runners build their pieces through, as a
+    stand-alone host program (csrc/kernels/tests/update_plan_check.cpp) built with AddressSanitizer
+    + UndefinedBehaviorSanitizer (hipcc's host compiler, else g++): on every plan of CELLS and the
+    in-line audit's segment-aligned plans with 3 and 8 PS its coalesced pieces per segment, the
+    merged list and tail_ok are exactly step_audit's."""
+    import os
+    import shutil
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = os.path.join(root, "distributed-deep-learning_amd", "csrc", "kernels", "tests",
+                       "update_plan_check.cpp")
+    hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
+    exe = str(tmp_path / "update_plan_check")
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+    if os.path.exists(hipcc):
+        cmd = [hipcc, "--offload-arch=gfx950", "-std=c++17", "-O1", "-g",
+               *[a for f in san for a in ("-Xarch_host", f)], src, "-o", exe]
+    elif shutil.which("g++"):
+        cmd = ["g++", "-std=c++17", "-O1", "-g", *san, src, "-o", exe]
+    else:
+        pytest.skip("needs hipcc or g++")
+    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    plans = {name: A.unit_pieces(cell_units(G.CELLS[name][0])[1], SEG_SETS) for name in G.CELLS}
+    for n in G.INLINE_LAUNCHES:
+        plans[f"inline-ps{n}"] = A.inline_pieces(inline_plan(n), SEG_SETS)
+    fmt = lambda v: "".join(f" {lo} {hi} {ps} {off};" for lo, hi, ps, off in v)  # noqa: E731
+    text, want = "", ""
+    for name, segs in plans.items():
+        text += f"plan {name}\n" + "".join(f"{s} {lo} {hi} {ps} {off}\n" for s, sp in enumerate(segs)
+                                           for lo, hi, ps, off in sp) + "end\n"
+        pieces, merged = A.coalesced(segs)   # (what segment_pieces returns for the units)
+        want += f"plan {name}\n" + "".join(f"seg {s}:{fmt(sp)}\n" for s, sp in enumerate(pieces))
+        want += f"merged:{fmt(merged)}\n"
+        ok = int(all(len(sp) <= A.TAIL_PIECES for sp in pieces))
+        want += f"tail_ok {ok} tail_v_ok 1\n"   # (every PS here has an aligned v)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
+               UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout == want
+    assert "tail_ok 0" in want and "tail_ok 1" in want   # both outcomes occur
+
+
+@pytest.mark.parametrize("num_ps", sorted(G.INLINE_LAUNCHES))
+def test_inline_launch_table_follows_the_runner_logic(num_ps):
+    """INLINE_LAUNCHES is what AsyncRunner::set_inline / step_inline give on the in-line audit's
+    plans: a segment rides when it has at most kTailPieces PS, whatever the others do."""
+    plan = inline_plan(num_ps)
+    pieces, merged = A.coalesced(A.inline_pieces(plan, SEG_SETS))
+    assert len(merged) == num_ps        # one PS, one piece: nothing coalesces across PS
+    n = A.expected_update_launches(pieces, merged, plan.tensor_offsets, per_segment=True)
+    print(f"inline {num_ps} PS: pieces per segment {[len(s) for s in pieces]}, {n} launches")
+    assert G.INLINE_LAUNCHES[num_ps] == n
+    if num_ps == 8:   # the per-segment fallback: six PS complete in segment 1
+        assert [len(s) for s in pieces] == [0, 6, 1, 1]
 
 
 @pytest.mark.parametrize("name", sorted(G.CELLS))
 def test_launch_table_follows_the_runner_logic(name):
-    """LAUNCHES[name] is what SyncRunner::set_units / step give on the cell's plan, planned by the
+    """LAUNCHES[name] is what UpdatePlan / SyncRunner::step give on the cell's plan, planned by the
     exchange's own planner; and the flagship plans ride everything."""
     kw, _, _, _, flags = G.CELLS[name]
     plan, (pieces, merged) = cell_pieces(kw)

@@ -48,8 +48,9 @@ not see it).  `stored_hyper` feeds exchange_reference.rule_step the values as th
 the tolerances stay.
 
 One more cell: the asynchronous W = 1 step over the xGMI plane with the in-line applies
-(async_runner.hip step_inline), flat plan with 3 PS, batch_size = B: the same op audit, the update
-with each PS's own t.
+(async_runner.hip step_inline), flat plan with 3 PS, batch_size = B, and with 8 PS at B = 5 (six
+shards in one segment: the stand-alone launches of the shared run_riding_backward): the same op
+audit, the update with each PS's own t, update_launches() against INLINE_LAUNCHES.
 
 Measured on one MI355X (docs/DESIGN.md "The native step, audited launch by launch" has the whole
 table): the file's 56 tests in 9.7 s, the slowest 0.83 s, a full audit at B = 33 0.7 s.  RMS-error
@@ -149,8 +150,9 @@ CELLS = {
     "flat-fc2-split": cell("flat", BATCHES, _fc2_split, "fc2-split"),
 }
 
-# runner.update_launches() of a step: the stand-alone optimizer launches.  Read off
-# SyncRunner::set_units / SyncRunner::step (runner.hip) and dual_then_b (engine_impl.h); the same
+# runner.update_launches() of a step: the stand-alone optimizer launches.  Read off UpdatePlan
+# (update_plan.h), SyncRunner::step / run_riding_backward (runner.hip) and dual_then_b
+# (engine_impl.h); the same
 # reading as code is step_audit.expected_update_launches, and tests/test_step_audit_cpu.py holds
 # this table against it on every plan.  Segments: 0 fc3, 1 conv4 + fc1 + fc2, 2 conv3, 3 conv2 + conv1;
 # segment s's update rides in segment s + 1's dual launch, segment 3's in conv1's weight-gradient
@@ -421,21 +423,35 @@ def test_step_audit(store, data, name, B):
     assert not fails, "\n".join(fails[:40])
 
 
-@pytest.mark.parametrize("B", BATCHES)
-def test_step_audit_async_inline(store, data, monkeypatch, B):
+# update_launches() of an in-line step by the number of PS, read off AsyncRunner::set_inline /
+# step_inline and run_riding_backward (runner.hip); tests/test_step_audit_cpu.py derives the same
+# numbers from step_audit.expected_update_launches(per_segment=True).
+# 3 PS, one per group of segments: the pieces ride in segments 2 and 3, and PS 0 = [0, 52160) is
+# exactly conv1 + conv2, so conv1's launch takes it.  8 PS, 1 / 1 / 6 per group: six PS complete in
+# segment 1, more than kTailPieces, so those six shards are launched stand-alone and the rest ride.
+INLINE_LAUNCHES = {3: 0, 8: 6}
+
+
+@pytest.mark.parametrize("num_ps,B", [pytest.param(3, B, id=str(B)) for B in BATCHES] +
+                         [pytest.param(8, 5, id="ps8-5")])
+def test_step_audit_async_inline(store, data, monkeypatch, num_ps, B):
     """The asynchronous W = 1 step over the xGMI plane with the in-line applies (async_runner.hip
-    step_inline, the default at one worker): segment-aligned flat plan, 3 PS, each PS's Adam as
-    tail blocks of the next segment's launch (tail blocks after the GEMM blocks) and the last
-    segment's in conv1's weight-gradient launch.  batch_size = B.  The same op audit; the update
-    with each PS's own step counter and the step size the runner forms (ops.adam_step_size)."""
+    step_inline, the default at one worker): segment-aligned flat plan, each PS's Adam as tail
+    blocks of the next segment's launch (tail blocks after the GEMM blocks) and the last segment's
+    in conv1's weight-gradient launch.  batch_size = B.  The same op audit; the update with each
+    PS's own step counter and the step size the runner forms (ops.adam_step_size).  With 3 PS
+    every segment rides; with 8 PS (1 / 1 / 6 per group of segments) segment 1 holds six shards,
+    more than one tail takes, and run_riding_backward launches those stand-alone while the other
+    segments still ride.  update_launches() after each step against INLINE_LAUNCHES."""
     from ddl_amd.ops import native
     monkeypatch.delenv("DDL_ASYNC_INLINE", raising=False)
     env = DistEnv(0, 1, 0, torch.device("cuda", 0))
     cfg = TrainConfig(mode="async", shard="flat", steps=2, batch_size=B, eval_every=0,
-                      engine="hip", quiet=True, exchange_backend="xgmi", lr=LR, keep_prob=KEEP)
+                      engine="hip", quiet=True, exchange_backend="xgmi", lr=LR, keep_prob=KEEP,
+                      num_ps=None if num_ps == 3 else num_ps)   # (3: the plan's own choice)
     tr = Trainer(cfg, env, dataset=data)
     ex = tr.exchange
-    assert tr.num_ps == 3 and ex.runner is not None
+    assert tr.num_ps == num_ps and ex.runner is not None
     for view, p in zip(param_views(tr.params, tr.plan.tensor_offsets), make_real_params()):
         view.copy_(p)
     for p, ps in tr.servers.items():   # the PS's private copies start from the worker's
@@ -448,7 +464,7 @@ def test_step_audit_async_inline(store, data, monkeypatch, B):
         assert ex.inline and ex.service_mode == "inline"
         ctx = StepCtx(tr)
         for step in (0, 1):
-            tag = f"async-inline B={B} step {step}"
+            tag = f"async-inline ps={num_ps} B={B} step {step}"
             x, y = A.batch(B, step)
             seed = A.STEP_SEEDS[step]
             before = state_of(tr)
@@ -457,6 +473,11 @@ def test_step_audit_async_inline(store, data, monkeypatch, B):
             ex.native_step(tr.engine, xg, y.to(DEV), KEEP, seed)
             ex.drain_round()
             torch.cuda.synchronize()
+            launches = ex.runner.update_launches()
+            if launches != INLINE_LAUNCHES[num_ps]:
+                fails.append(f"{tag}: update_launches() {launches}, the table says "
+                             f"{INLINE_LAUNCHES[num_ps]}")
+            lines.append(f"AUDIT-LAUNCHES {tag}: {launches}")
             bufs = read_buffers(ctx, B, xg)
             fails += untouched(ctx, B, snap, bufs, tag)
             P = [p.cpu().clone() for p in param_views(before["params"], ctx.offsets)]
