@@ -1,18 +1,14 @@
 """Multi-process helpers for the gloo (CPU) protocol tests: one spawned process per rank."""
 import os
-import sys
 import traceback
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from onecard import enter
 
 
 def _setup(rank, world, port):
-    if ROOT not in sys.path:
-        sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
-                      WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    enter(rank, world, port)
     torch.set_num_threads(1)
 
 

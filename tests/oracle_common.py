@@ -31,8 +31,14 @@ def interior(name, t):
     return t[:, 2:-2, 2:-2, :] if name in HALO_BUFS else t
 
 
-def bits(t):
+def bits(t, host=False):
+    """t's bit pattern (float32 as int32) on t's device, or with host=True on the CPU."""
+    t = t.detach().cpu() if host else t.detach()
     return t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t.contiguous()
+
+
+def host_bits(t):
+    return bits(t, host=True)
 
 
 def prepare(ctx, B, inputs):

@@ -16,17 +16,11 @@ import async_replay as ar
 import exchange_reference as xr
 from conftest import free_port
 from dist_helpers import _setup, spawn, train_rank
+from onecard import f32
+from oracle_common import bits
 
 from ddl_amd.ops import accum as A
 from ddl_amd.ops import clip as C
-
-
-def bits(t):
-    return t.detach().contiguous().view(torch.int32)
-
-
-def f32(x):
-    return float(np.float32(x))
 
 
 NEG0 = int(np.float32(-0.0).view(np.int32))

@@ -26,19 +26,15 @@ from ddl_amd.ops import accum as A
 from ddl_amd.ops import clip as C
 from ddl_amd.ops import native
 
+import onecard as oc
+from onecard import f32
+from oracle_common import host_bits as bits
+
 pytestmark = pytest.mark.gpu
 
 CH = C.CHUNK
 DEV = torch.device("cuda", 0)
 KS = [2, 3, 5]
-
-
-def bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
-
-
-def f32(x):
-    return float(np.float32(x))
 
 
 def same_pair(got, want):
@@ -412,130 +408,50 @@ def test_clip_reads_the_effective_gradient(data):
 
 
 # ---- e. the exchanges on one card ---------------------------------------------------------------------------
-# Worker processes share the one GPU (default group over gloo), as tests/test_clip_gpu.py runs
-# them.  At most two workers beside this process, each run under a time limit of its own.
+# Worker processes share the one GPU (tests/onecard.py).  At most two workers beside this
+# process, each job under one time limit.
 LIMIT_S = 150
 XB, XK, XSTEPS, ASTEPS = 5, 2, 2, 4
-ADAM_K = 0
-
-
-def _spawn(fn, world, *args):
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    kids = [ctx.Process(target=fn, args=(r, world, *args)) for r in range(world)]
-    for k in kids:
-        k.start()
-    for k in kids:
-        k.join(timeout=LIMIT_S)
-    late = [k for k in kids if k.is_alive()]
-    for k in late:
-        k.kill()
-        k.join()
-    assert not late, f"{len(late)} worker(s) still running after {LIMIT_S} s"
-    assert all(k.exitcode == 0 for k in kids), [k.exitcode for k in kids]
-
-
-def _env(rank, world, port):
-    import os
-    import sys
-    from conftest import ROOT
-    if ROOT not in sys.path:
-        sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
-                      WORLD_SIZE=str(world), LOCAL_RANK=str(rank), DDL_DIST_BACKEND="gloo",
-                      DDL_XGMI_TIMEOUT_S="20")
-
-
-def _canon(params, offsets):
-    from ddl_amd.models.layout import TENSORS
-    return torch.cat([params[offsets[t.index]:offsets[t.index] + t.numel] for t in TENSORS])
 
 
 def _sync_rank(rank, world, port, outdir, kw):
     """One rank of an accumulated synchronous run on the xGMI exchange: XSTEPS steps of XK
     micro-batches of XB."""
     import os
-    import traceback
-    _env(rank, world, port)
-    try:
-        import torch.distributed as dist
-        from ddl_amd.config import TrainConfig
-        from ddl_amd.parallel.comm import init_distributed
-        from ddl_amd.parallel.roles import Trainer
+    with oc.rank_session(rank, world, port) as me:
         from ddl_amd.utils.data import synthetic_mnist
-        env = init_distributed()
-        cfg = TrainConfig(mode="sync", steps=XSTEPS, batch_size=XB, eval_every=0, engine="hip",
-                          quiet=True, data_sharding="stride", exchange_backend="xgmi",
-                          accum_steps=XK, **kw)
-        tr = Trainer(cfg, env, dataset=synthetic_mnist(400, 100, seed=5))
-        ex = tr.exchange
-        assert getattr(ex, "native", False) and ex.peer is not None, "xgmi path not taken"
-        for i in range(XSTEPS):
-            tr.train_step(i)
-            torch.cuda.synchronize()
-        ex.check()
-        torch.save({"params": _canon(tr.params, tr.plan.tensor_offsets).cpu(),
-                    "t": {p: s.t for p, s in tr.servers.items()}, "steps": tr.global_step},
-                   os.path.join(outdir, f"rank{rank}.pt"))
-        dist.barrier()
-        ex.close()
-        dist.barrier()
-        dist.destroy_process_group()
-    except Exception:
-        traceback.print_exc()
-        raise
+        tr = oc.xgmi_trainer(me.env, "sync", XSTEPS, XB, synthetic_mnist(400, 100, seed=5),
+                             accum_steps=XK, **kw)
+        rec = oc.sync_rank_record(tr, XSTEPS, per_step=oc.sync_each_step)
+        torch.save(rec, os.path.join(outdir, f"rank{rank}.pt"))
+        me.close_single(tr.exchange)
 
 
-def effective_grad(eng, grads, acc, ranges, data, r, world, s, K, cfg):
-    """Rank r's effective gradient of step s into `grads` (HIP engine, the kernel tested in a)."""
-    from ddl_amd.ops import rng
-    from ddl_amd.utils.data import batch_indices
-    ops = native.ops()
-    for j in range(K):
-        lo, hi = batch_indices(s * K + j, XB, data.total_batch, r, world, cfg["data_sharding"])
-        eng.forward_backward(data.x_train[lo:hi], data.y_train[lo:hi], cfg["keep_prob"],
-                             rng.step_seed(cfg["seed"], r, s * K + j))
-        if K > 1:
-            ops.accum_grads(grads, acc, ranges, A.mode_of(j, K), K)
+def effective_grad(K, total, ranges):
+    """A grad_hook: rank r's effective gradient of step s into the engine's gradient buffer (K
+    micro-batches, each on its own batch and dropout seed, through the kernel tested in a)."""
+    acc = torch.zeros(total, device=DEV)
+
+    def hook(ge, r, s):
+        for j in range(K):
+            ge.backward(r, s * K + j, s * K + j)
+            if K > 1:
+                native.ops().accum_grads(ge.grads, acc, ranges, A.mode_of(j, K), K)
+    return hook
 
 
 _SIM = {}
 
 
 def simulate_sync(world, K=XK, steps=XSTEPS):
-    """The one-process PS simulation: every rank's effective gradient (K micro-batches on its own
-    batches and dropout seeds), summed in rank order from 0 (exchange_reference.rank_order_sum),
+    """The one-process PS simulation (onecard.simulate_sync) fed every rank's effective gradient:
     one native Adam step per step — steps, not micro-batches."""
-    if (world, K) in _SIM:
-        return _SIM[(world, K)]
-    import exchange_reference as xr
-    from ddl_amd.models.hip_engine import HipEngine
-    from ddl_amd.models.mnist_cnn import init_params_
-    from ddl_amd.ops.adam import AdamHyper, adam_coeffs
-    from ddl_amd.parallel.sharding import make_plan
-    from ddl_amd.utils.data import synthetic_mnist
-    ops = native.ops()
-    data = synthetic_mnist(400, 100, seed=5).to(DEV)
-    plan = make_plan("none", 1)
-    params = torch.zeros(plan.total, device=DEV)
-    init_params_(params, plan.tensor_offsets, 0)
-    grads = torch.zeros_like(params)
-    acc = torch.zeros_like(params)
-    m, v = torch.zeros_like(params), torch.zeros_like(params)
-    eng = HipEngine(params, grads, plan.tensor_offsets, batch=XB, graph=False, eval_chunk=XB)
-    ranges = C.payload_ranges(plan.tensor_offsets)
-    h = AdamHyper()
-    cfg = dict(data_sharding="stride", keep_prob=0.5, seed=0)
-    for step in range(steps):
-        gs = []
-        for r in range(world):
-            effective_grad(eng, grads, acc, ranges, data, r, world, step, K, cfg)
-            torch.cuda.synchronize()
-            gs.append(grads.cpu())
-        total = xr.rank_order_sum(gs).to(DEV)
-        ops.adam_flat(params, total, m, v, adam_coeffs(h, step + 1), h.beta1, h.beta2, h.eps, 1.0)
-        torch.cuda.synchronize()
-    _SIM[(world, K)] = _canon(params, plan.tensor_offsets).cpu()
+    if (world, K) not in _SIM:
+        from ddl_amd.parallel.sharding import make_plan
+        plan = make_plan("none", 1)
+        hook = effective_grad(K, plan.total, C.payload_ranges(plan.tensor_offsets))
+        _SIM[(world, K)] = oc.simulate_sync(world, steps, XB, oc.dataset_on_card(400, 100), plan,
+                                            grad_hook=hook)
     return _SIM[(world, K)]
 
 
@@ -545,11 +461,9 @@ def test_xgmi_sync_w2(tmp_path, shard):
     """Sync W = 2 over xGMI on one card, K = 2, 2 steps of B = 5: the replicas agree bit for bit
     and equal the simulation fed each rank's effective gradient; every PS counted 2 steps."""
     from conftest import free_port
-    import os
     want = simulate_sync(2)
-    _spawn(_sync_rank, 2, free_port(), str(tmp_path), dict(shard=shard))
-    recs = [torch.load(os.path.join(tmp_path, f"rank{r}.pt"), weights_only=False)
-            for r in range(2)]
+    oc.run_ranks(_sync_rank, 2, free_port(), str(tmp_path), dict(shard=shard), limit_s=LIMIT_S)
+    recs = oc.load_ranks(tmp_path, 2)
     assert torch.equal(bits(recs[0]["params"]), bits(recs[1]["params"]))
     for rec in recs:
         assert rec["steps"] == XSTEPS and all(t == XSTEPS for t in rec["t"].values())
@@ -572,65 +486,29 @@ def test_forced_rccl_rehearsal_w1():
     for i in range(XSTEPS):
         tr.train_step(i)
         torch.cuda.synchronize()
-    got = _canon(tr.params, tr.plan.tensor_offsets).cpu()
+    got = oc.canon(tr.params, tr.plan.tensor_offsets).cpu()
     assert all(s.t == XSTEPS for s in tr.servers.values())
     tr.exchange.close()
     assert torch.equal(bits(got), bits(want))
 
 
 def _async_rank(rank, world, port, outdir, kw):
-    """One rank of an accumulated asynchronous run on the xGMI data plane, ASTEPS steps (the
-    set-up of tests/test_clip_gpu.py::_async_rank; W = 1 takes the in-line applies)."""
+    """One rank of an accumulated asynchronous run on the xGMI data plane, ASTEPS steps (W = 1
+    takes the in-line applies)."""
     import os
-    import traceback
-    _env(rank, world, port)
-    try:
-        import torch.distributed as dist
-        from ddl_amd.config import TrainConfig
-        from ddl_amd.parallel.async_xgmi import AsyncPeerExchange
-        from ddl_amd.parallel.comm import init_distributed
-        from ddl_amd.parallel.roles import Trainer
+    with oc.rank_session(rank, world, port) as me:
         from ddl_amd.utils.data import synthetic_mnist
-        env = init_distributed()
-        cfg = TrainConfig(mode="async", steps=ASTEPS, batch_size=XB, eval_every=0, engine="hip",
-                          quiet=True, data_sharding="stride", exchange_backend="xgmi",
-                          check_provenance=True, watchdog_s=120.0, accum_steps=XK, **kw)
-        tr = Trainer(cfg, env, dataset=synthetic_mnist(2000, 500, seed=5))
-        ex = tr.exchange
-        assert isinstance(ex, AsyncPeerExchange) and ex.runner is not None
-        init = tr.params.clone()
-        ex.steps = ASTEPS
-        ex.start()
-        assert ex.inline == (world == 1)
-        if world > 1:
-            torch.cuda.synchronize()
-            dist.barrier()
-        for i in range(ASTEPS):
-            tr.train_step(i)
-            torch.cuda.synchronize()
-        ex.join()
-        ex.verify_provenance()
-        torch.cuda.synchronize()
-        assert ex.peer.error() == 0, ex.peer.error()
-        P = tr.plan.num_ps
-        torch.save({"init": init.cpu(), "params": tr.params.cpu(),
-                    "ps": {p: dict(m=s.m.cpu(), v=s.v.cpu(), t=s.t)
-                           for p, s in tr.servers.items()},
-                    "provenance": list(ex.provenance), "steps": tr.global_step,
-                    "ranges": [tr.plan.ps_segments(p)[0] for p in range(P)],
-                    "hosts": [tr.plan.host_rank(p, world) for p in range(P)],
-                    "offsets": list(tr.plan.tensor_offsets), "total": tr.plan.total,
-                    "cfg": cfg.to_dict()},
-                   os.path.join(outdir, f"rank{rank}.pt"))
-        if world > 1:
-            dist.barrier()
-        ex.close()
-        if world > 1:
-            dist.barrier()
-            dist.destroy_process_group()
-    except Exception:
-        traceback.print_exc()
-        raise
+        tr = oc.xgmi_trainer(me.env, "async", ASTEPS, XB, synthetic_mnist(2000, 500, seed=5),
+                             accum_steps=XK, **kw)
+        assert tr.exchange.runner is not None
+
+        def started(ex):
+            assert ex.inline == (world == 1)
+
+        rec = oc.async_rank_record(tr, world, ASTEPS, per_step=oc.sync_each_step,
+                                   after_start=started)
+        torch.save(rec, os.path.join(outdir, f"rank{rank}.pt"))
+        me.close_single(tr.exchange)
 
 
 @pytest.mark.slow
@@ -642,52 +520,16 @@ def test_xgmi_async_equals_its_replay(tmp_path, world, kw):
     """Async over xGMI, K = 2, 4 steps, W = 1 in-line applies and W = 2 on the arrival board: the
     run equals the replay of its recorded apply orders with a gradient function that accumulates;
     every PS applied W * 4 pushes and logged one provenance row per step, worker and PS."""
-    import os
     import async_replay as ar
     from conftest import free_port
-    from ddl_amd.models.hip_engine import HipEngine
-    from ddl_amd.ops.adam import AdamHyper, adam_coeffs
-    from ddl_amd.utils.data import synthetic_mnist
-    _spawn(_async_rank, world, free_port(), str(tmp_path), kw)
-    recs = [torch.load(os.path.join(tmp_path, f"rank{r}.pt"), weights_only=False)
-            for r in range(world)]
-    hosts, ranges = recs[0]["hosts"], recs[0]["ranges"]
-    rows = [e for rec in recs for e in rec["provenance"]]
-    assert len(rows) == world * ASTEPS * len(hosts)
+    oc.run_ranks(_async_rank, world, free_port(), str(tmp_path), kw, limit_s=LIMIT_S)
+    recs = oc.load_ranks(tmp_path, world)
+    rows, order = oc.recorded_orders(recs, world, ASTEPS)
+    assert len(rows) == world * ASTEPS * len(recs[0]["hosts"])
     assert all(rec["steps"] == ASTEPS for rec in recs)
-    order = ar.apply_orders(rows, world, ASTEPS)
     print("orders", {p: ar.order_string(o) for p, o in order.items()})
-    cfg = recs[0]["cfg"]
-    data = synthetic_mnist(2000, 500, seed=5).to(DEV)
-    params = torch.zeros(recs[0]["total"], device=DEV)
-    grads = torch.zeros_like(params)
-    acc = torch.zeros_like(params)
-    eng = HipEngine(params, grads, recs[0]["offsets"], batch=XB, graph=False, eval_chunk=XB)
     table = C.payload_ranges(recs[0]["offsets"])
-    h = AdamHyper(lr=f32(cfg["lr"]), beta1=f32(0.9), beta2=f32(0.999))
-    ops = native.ops()
-
-    def grad_fn(r, s, params_r):
-        params.copy_(params_r)
-        effective_grad(eng, grads, acc, table, data, r, world, s, XK, cfg)
-        return grads.clone()
-
-    def update_fn(p, st, g, t):
-        ops.update_flat(ADAM_K, st.w, g, st.m, st.v, adam_coeffs(h, t), 0.9, 0.999, 1e-8, 0.0, 1.0)
-
-    want, state = ar.replay(order, ranges, recs[0]["init"].to(DEV), world, ASTEPS, grad_fn,
-                            update_fn)
-    torch.cuda.synchronize()
-    for r in range(world):
-        for lo, n in table:
-            assert torch.equal(bits(recs[r]["params"][lo:lo + n]), bits(want[r][lo:lo + n])), r
-    for p in range(len(hosts)):
-        got = recs[hosts[p]]["ps"][p]
-        w, m, v, t = state[p]
-        assert got["t"] == t == world * ASTEPS
-        lo0 = ranges[p][0]
-        for lo, n in table:
-            a, b = max(lo, ranges[p][0]) - lo0, min(lo + n, ranges[p][1]) - lo0
-            if a < b:
-                assert torch.equal(bits(got["m"][a:b]), bits(m[a:b]))
-                assert torch.equal(bits(got["v"][a:b]), bits(v[a:b]))
+    want, state = oc.replay_async(recs, world, order, ASTEPS,
+                                  grad_hook=effective_grad(XK, recs[0]["total"], table))
+    oc.assert_payload_equals_replay(recs, world, want, state, table)
+    assert all(t == world * ASTEPS for (_, _, _, t) in state.values())

@@ -43,145 +43,47 @@ Adam, 4.8e-6 with momentum and 7.4e-7 with SGD (max abs).  docs/DESIGN.md "Async
 replayed in apply order" lists every cell's orders.
 """
 import os
-import sys
 import time
-import traceback
 
 import pytest
 import torch
 
 import async_replay as ar
-from conftest import ROOT, free_port
+import onecard as oc
+from conftest import free_port
 
 pytestmark = [pytest.mark.gpu, pytest.mark.slow]
 
 STEPS = 6
 SLEEP_S = 0.2
-ADAM, MOMENTUM = 0, 1  # update.h UpdKind
 
 
 def _rank(rank, world, port, outdir, kw):
-    """One rank: the set-up of tests/test_xgmi_gpu.py::_async_rank, the steps driven one by one
-    (the skew cell sleeps between them)."""
-    if ROOT not in sys.path:
-        sys.path.insert(0, ROOT)
+    """One rank, its steps driven one by one (the skew cell sleeps between them)."""
     kw = dict(kw)
     extra_env = kw.pop("_env", {})
     skew = kw.pop("_skew", ())
     kw.pop("_ps", None)
     batch = kw.pop("_batch")
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
-                      WORLD_SIZE=str(world), LOCAL_RANK=str(rank), DDL_DIST_BACKEND="gloo",
-                      DDL_XGMI_TIMEOUT_S="20")
-    os.environ.update(extra_env)
-    try:
-        import torch.distributed as dist
-        from ddl_amd.config import TrainConfig
-        from ddl_amd.parallel.async_xgmi import AsyncPeerExchange
-        from ddl_amd.parallel.comm import init_distributed
-        from ddl_amd.parallel.roles import Trainer
+    with oc.rank_session(rank, world, port, env=extra_env, on_device_0=True) as me:
         from ddl_amd.utils.data import synthetic_mnist
-        env = init_distributed()
-        assert env.device.index == 0
-        cfg = TrainConfig(mode="async", steps=STEPS, batch_size=batch, eval_every=0,
-                          engine="hip", quiet=True, data_sharding="stride",
-                          exchange_backend="xgmi", check_provenance=True, watchdog_s=120.0, **kw)
-        tr = Trainer(cfg, env, dataset=synthetic_mnist(2000, 500, seed=5))
+        tr = oc.xgmi_trainer(me.env, "async", STEPS, batch, synthetic_mnist(2000, 500, seed=5),
+                             **kw)
         ex = tr.exchange
-        assert isinstance(ex, AsyncPeerExchange), type(ex)
         want_native = extra_env.get("DDL_ASYNC_NATIVE", "1") == "1"
         assert (ex.runner is not None) == want_native, "native async step not taken"
-        init = tr.params.clone()
-        ex.steps = STEPS
-        ex.start()
-        if tr.servers:
-            assert ex.service_mode == "host", ex.service_mode  # (the control: not in-line)
-        if world > 1:  # the ranks start together: their pushes do meet at the PS
-            torch.cuda.synchronize()
-            dist.barrier()
-        for i in range(STEPS):
+
+        def started(ex):
+            if tr.servers:
+                assert ex.service_mode == "host", ex.service_mode  # (the control: not in-line)
+
+        def maybe_sleep(i):
             if rank == 1 and i in skew:
                 time.sleep(SLEEP_S)
-            tr.train_step(i)
-        ex.join()
-        ex.verify_provenance()
-        torch.cuda.synchronize()
-        assert ex.peer.error() == 0, ex.peer.error()
-        P = tr.plan.num_ps
-        torch.save({"init": init.cpu(), "params": tr.params.cpu(),
-                    "ps": {p: dict(w=s.params.cpu(), m=s.m.cpu(),
-                                   v=None if s.v is None else s.v.cpu(), t=s.t)
-                           for p, s in tr.servers.items()},
-                    "provenance": list(ex.provenance), "served": ex.served,
-                    "ranges": [tr.plan.ps_segments(p)[0] for p in range(P)],
-                    "hosts": [tr.plan.host_rank(p, world) for p in range(P)],
-                    "offsets": list(tr.plan.tensor_offsets), "total": tr.plan.total,
-                    "cfg": cfg.to_dict()},
-                   os.path.join(outdir, f"rank{rank}.pt"))
-        if world > 1:
-            dist.barrier()
-        ex.close()
-        if world > 1:
-            dist.barrier()
-            dist.destroy_process_group()
-    except Exception:
-        traceback.print_exc()
-        raise
 
-
-_DATA = []
-
-
-def _data():
-    """The ranks' dataset on the card: made once, read by every cell's replay."""
-    if not _DATA:
-        from ddl_amd.utils.data import synthetic_mnist
-        _DATA.append(synthetic_mnist(2000, 500, seed=5).to(torch.device("cuda", 0)))
-    return _DATA[0]
-
-
-def _replay(recs, world, order):
-    """The run again in this process, in the recorded order, with the engine's gradients and
-    ops.update_flat."""
-    import numpy as np
-    from ddl_amd.models.hip_engine import HipEngine
-    from ddl_amd.ops import native, rng
-    from ddl_amd.ops.adam import AdamHyper, adam_coeffs
-    from ddl_amd.utils.data import batch_indices
-    dev = torch.device("cuda", 0)
-    cfg = recs[0]["cfg"]
-    B = cfg["batch_size"]
-    data = _data()
-    params = torch.zeros(recs[0]["total"], device=dev)
-    grads = torch.zeros_like(params)
-    eng = HipEngine(params, grads, recs[0]["offsets"], batch=B, graph=False, eval_chunk=B)
-    f32 = lambda x: float(np.float32(x))  # noqa: E731
-    # the xGMI service holds lr and the betas as float32 and widens them for the step size
-    # (update.h adam_step_size; tests/test_numerics_cpu.py pins that to adam_coeffs on the same
-    # operands)
-    h = AdamHyper(lr=f32(cfg["lr"]), beta1=f32(0.9), beta2=f32(0.999))
-    opt = cfg["optimizer"]
-    mu = {"adam": 0.0, "momentum": cfg["momentum"], "sgd": 0.0}[opt]
-
-    def grad_fn(r, s, params_r):
-        params.copy_(params_r)
-        lo, hi = batch_indices(s, B, data.total_batch, r, world, cfg["data_sharding"])
-        eng.forward_backward(data.x_train[lo:hi], data.y_train[lo:hi], cfg["keep_prob"],
-                             rng.step_seed(cfg["seed"], r, s))
-        return grads.clone()
-
-    def update_fn(p, st, g, t):
-        if opt == "adam":
-            native.ops().update_flat(ADAM, st.w, g, st.m, st.v, adam_coeffs(h, t), 0.9, 0.999,
-                                     1e-8, 0.0, 1.0)
-        else:
-            native.ops().update_flat(MOMENTUM, st.w, g, st.m, None, f32(cfg["lr"]), 0.0, 0.0,
-                                     0.0, mu, 1.0)
-
-    out = ar.replay(order, recs[0]["ranges"], recs[0]["init"].to(dev), world, STEPS, grad_fn,
-                    update_fn)
-    torch.cuda.synchronize()
-    return out
+        rec = oc.async_rank_record(tr, world, STEPS, before_step=maybe_sleep, after_start=started)
+        torch.save(rec, os.path.join(outdir, f"rank{rank}.pt"))
+        me.close_single(ex)
 
 
 def _spans(ranges, offsets):
@@ -225,55 +127,28 @@ CELLS = [
 
 @pytest.mark.parametrize("world,kw", CELLS)
 def test_async_xgmi_run_equals_its_replay(tmp_path, world, kw):
-    import torch.multiprocessing as mp
     t_start = time.perf_counter()
-    mp.spawn(_rank, args=(world, free_port(), str(tmp_path), kw), nprocs=world, join=True)
+    oc.run_ranks(_rank, world, free_port(), str(tmp_path), kw, limit_s=oc.LIMIT_S)
     t_run = time.perf_counter() - t_start
-    recs = [torch.load(os.path.join(tmp_path, f"rank{r}.pt"), weights_only=False)
-            for r in range(world)]
+    recs = oc.load_ranks(tmp_path, world)
     hosts, ranges, offsets = recs[0]["hosts"], recs[0]["ranges"], recs[0]["offsets"]
-    num_ps = len(hosts)
-    assert num_ps == kw.get("_ps", kw.get("num_ps", world))
+    assert len(hosts) == kw.get("_ps", kw.get("num_ps", world))
     for rec in recs[1:]:
         assert torch.equal(rec["init"], recs[0]["init"])
         assert rec["ranges"] == ranges and rec["offsets"] == offsets
-    log = [e for rec in recs for e in rec["provenance"]]
-    assert len(log) == num_ps * world * STEPS  # the xGMI service logs every apply
-    order = ar.apply_orders(log, world, STEPS)
+    _, order = oc.recorded_orders(recs, world, STEPS)
     orders = {p: ar.order_string(o) for p, o in order.items()}
     if kw.get("_skew"):
         assert ar.staleness_exercised(order, STEPS), f"staleness not exercised: {orders}"
-    params, state = _replay(recs, world, order)
+    params, state = oc.replay_async(recs, world, order, STEPS)
     print(f"cell: run {t_run:.1f} s, replay {time.perf_counter() - t_start - t_run:.1f} s; "
           f"orders {orders}")
-    fails = []
-    spans = _spans(ranges, offsets)
-    for r in range(world):
-        got = recs[r]["params"]
-        lines = ar.mismatch_report(f"worker {r}", got, params[r].cpu(), spans)
-        if not lines and not torch.equal(got, params[r].cpu()):
-            lines = [f"worker {r}: differs outside every tensor (alignment padding)"]
-        fails += lines
-    for p in range(num_ps):
-        got = recs[hosts[p]]["ps"][p]
-        w, m, v, t = state[p]
-        lo = ranges[p][0]
-        inner = [(a - lo, b - lo, label) for (a, b, label) in spans if label.startswith(f"PS {p} ")]
-        if got["t"] != t:
-            fails.append(f"PS {p}: t {got['t']}, replay {t}")
-        for name, a, b in (("params", got["w"], w), ("m", got["m"], m), ("v", got["v"], v)):
-            if a is None:
-                assert name == "v" and kw.get("optimizer") in ("momentum", "sgd")
-                continue
-            lines = ar.mismatch_report(f"PS {p} {name}", a, b.cpu(), inner)
-            if not lines and not torch.equal(a, b.cpu()):
-                lines = [f"PS {p} {name}: differs in the alignment padding"]
-            fails += lines
+    fails = oc.replay_mismatches(recs, world, params, state, _spans(ranges, offsets))
     assert not fails, f"orders {orders}\n" + "\n".join(fails[:40])
     # the comparison is sharp on this very run: one pair of adjacent applies swapped moves it
     for p, i, sw in ar.adjacent_swaps(order):
         try:
-            other, _ = _replay(recs, world, sw)
+            other, _ = oc.replay_async(recs, world, sw, STEPS)
         except ar.ReplayError:
             continue
         moved = max(float((a - b).abs().max()) for a, b in zip(other, params))

@@ -16,18 +16,12 @@ import torch
 import async_replay as ar
 from conftest import free_port
 from dist_helpers import spawn, train_rank
+from onecard import f32
+from oracle_common import bits
 
 from ddl_amd.ops import clip as C
 
 CH = C.CHUNK
-
-
-def bits(t):
-    return t.detach().contiguous().view(torch.int32)
-
-
-def f32(x):
-    return float(np.float32(x))
 
 
 def ulp(x):

@@ -23,18 +23,14 @@ import torch
 from ddl_amd.ops import clip as C
 from ddl_amd.ops import native
 
+import onecard as oc
+from onecard import f32
+from oracle_common import host_bits as bits
+
 pytestmark = pytest.mark.gpu
 
 CH = C.CHUNK
 DEV = torch.device("cuda", 0)
-
-
-def bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
-
-
-def f32(x):
-    return float(np.float32(x))
 
 
 def gpu_clip(buf, ranges, max_norm, max_grid=0):
@@ -279,125 +275,55 @@ def test_native_step_w1(data, B, rule):
 
 
 # ---- c. the exchanges on one card ---------------------------------------------------------------
-# Worker processes share the one GPU (default group over gloo), as tests/test_xgmi_gpu.py runs
-# them.  At most two workers beside this process, each run under a time limit of its own.
+# Worker processes share the one GPU (tests/onecard.py).  At most two workers beside this
+# process, each job under one time limit.
 LIMIT_S = 150
 XB, XSTEPS, ASTEPS = 5, 2, 4
-ADAM_K = 0
 
 
-def _spawn(fn, world, *args):
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    kids = [ctx.Process(target=fn, args=(r, world, *args)) for r in range(world)]
-    for k in kids:
-        k.start()
-    for k in kids:
-        k.join(timeout=LIMIT_S)
-    late = [k for k in kids if k.is_alive()]
-    for k in late:
-        k.kill()
-        k.join()
-    assert not late, f"{len(late)} worker(s) still running after {LIMIT_S} s"
-    assert all(k.exitcode == 0 for k in kids), [k.exitcode for k in kids]
-
-
-def _env(rank, world, port):
-    import os
-    import sys
-    from conftest import ROOT
-    if ROOT not in sys.path:
-        sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
-                      WORLD_SIZE=str(world), LOCAL_RANK=str(rank), DDL_DIST_BACKEND="gloo",
-                      DDL_XGMI_TIMEOUT_S="20")
-
-
-def _canon(params, offsets):
-    from ddl_amd.models.layout import TENSORS
-    return torch.cat([params[offsets[t.index]:offsets[t.index] + t.numel] for t in TENSORS])
+def _pairs(tr, i):
+    torch.cuda.synchronize()
+    return {"pairs": tuple(tr.clip_out.tolist()), "coefs": float(tr.clip_out[1])}
 
 
 def _sync_rank(rank, world, port, outdir, kw):
     """One rank of a clipped synchronous run on the xGMI exchange: XSTEPS steps of batch XB."""
     import os
-    import traceback
-    _env(rank, world, port)
-    try:
-        import torch.distributed as dist
-        from ddl_amd.config import TrainConfig
-        from ddl_amd.parallel.comm import init_distributed
-        from ddl_amd.parallel.roles import Trainer
+    with oc.rank_session(rank, world, port) as me:
         from ddl_amd.utils.data import synthetic_mnist
-        env = init_distributed()
-        cfg = TrainConfig(mode="sync", steps=XSTEPS, batch_size=XB, eval_every=0, engine="hip",
-                          quiet=True, data_sharding="stride", exchange_backend="xgmi", **kw)
-        tr = Trainer(cfg, env, dataset=synthetic_mnist(400, 100, seed=5))
-        ex = tr.exchange
-        assert getattr(ex, "native", False) and ex.peer is not None, "xgmi path not taken"
-        pairs = []
-        for i in range(XSTEPS):
-            tr.train_step(i)
-            torch.cuda.synchronize()
-            pairs.append(tuple(tr.clip_out.tolist()))
-        ex.check()
-        torch.save({"params": _canon(tr.params, tr.plan.tensor_offsets).cpu(), "pairs": pairs,
-                    "t": {p: s.t for p, s in tr.servers.items()}},
-                   os.path.join(outdir, f"rank{rank}.pt"))
-        dist.barrier()
-        ex.close()
-        dist.barrier()
-        dist.destroy_process_group()
-    except Exception:
-        traceback.print_exc()
-        raise
+        tr = oc.xgmi_trainer(me.env, "sync", XSTEPS, XB, synthetic_mnist(400, 100, seed=5), **kw)
+        rec = oc.sync_rank_record(tr, XSTEPS, per_step=_pairs)
+        torch.save(rec, os.path.join(outdir, f"rank{rank}.pt"))
+        me.close_single(tr.exchange)
 
 
 def _simulate_sync(world, clip_norm, steps=XSTEPS, B=XB):
-    """The one-process PS simulation: every rank's HIP-engine gradient on its own batch and
-    dropout seed, clipped by the kernel tested above, summed in rank order from 0
-    (exchange_reference.rank_order_sum), one native Adam step per global step.  Each step is also
-    held against the fp64 rule of exchange_reference (rank_order_sum + rule_step, what sync_round
-    applies per region) within the exchange tests' bounds: 1e-6 absolute on w, 1e-6 relative on m
-    and v."""
+    """The one-process PS simulation (onecard.simulate_sync) with every rank's gradient clipped
+    by the kernel tested above.  Each step is also held against the fp64 rule of
+    exchange_reference (rule_step on the rank-order sum, what sync_round applies per region)
+    within the exchange tests' bounds: 1e-6 absolute on w, 1e-6 relative on m and v."""
     import exchange_reference as xr
-    from ddl_amd.models.hip_engine import HipEngine
-    from ddl_amd.models.mnist_cnn import init_params_
-    from ddl_amd.ops import rng
     from ddl_amd.ops.adam import AdamHyper, adam_coeffs
     from ddl_amd.parallel.sharding import make_plan
-    from ddl_amd.utils.data import synthetic_mnist, batch_indices
     ops = native.ops()
-    data = synthetic_mnist(400, 100, seed=5).to(DEV)
     plan = make_plan("none", 1)
-    params = torch.zeros(plan.total, device=DEV)
-    init_params_(params, plan.tensor_offsets, 0)
-    grads = torch.zeros_like(params)
-    m, v = torch.zeros_like(params), torch.zeros_like(params)
-    eng = HipEngine(params, grads, plan.tensor_offsets, batch=B, graph=False, eval_chunk=B)
     ranges = C.payload_ranges(plan.tensor_offsets)
     out = torch.zeros(2, dtype=torch.float32, device=DEV)
     h = AdamHyper()
     pairs = [[] for _ in range(world)]
-    for step in range(steps):
-        gs = []
-        for r in range(world):
-            lo, hi = batch_indices(step, B, data.total_batch, r, world, "stride")
-            eng.forward_backward(data.x_train[lo:hi], data.y_train[lo:hi], 0.5,
-                                 rng.step_seed(0, r, step))
-            if clip_norm > 0:
-                ops.clip_grads(grads, ranges, clip_norm, out)
-                pairs[r].append(tuple(out.tolist()))
-            gs.append(grads.cpu())
-        acc = xr.rank_order_sum(gs).to(DEV)
-        lr_t = adam_coeffs(h, step + 1)
+
+    def clipped(ge, r, step):
+        oc.plain_grad(ge, r, step)
+        if clip_norm > 0:
+            ops.clip_grads(ge.grads, ranges, clip_norm, out)
+            pairs[r].append(tuple(out.tolist()))
+
+    def fp64_rule(step, params, acc, m, v, before):
         # (sync_round's two ingredients, with the betas as the kernels hold them: float32.  From
         # v = 0 the difference between 1 - 0.999 and 1 - float32(0.999), 4.7e-5 relative, would
         # otherwise be all there is to see)
-        w64, m64, v64 = xr.rule_step(xr.ADAM, params, m, v, acc, lr_t, b1=f32(h.beta1),
-                                     b2=f32(h.beta2), eps=f32(h.eps))
-        ops.adam_flat(params, acc, m, v, lr_t, h.beta1, h.beta2, h.eps, 1.0)
-        torch.cuda.synchronize()
+        w64, m64, v64 = xr.rule_step(xr.ADAM, *before, acc, adam_coeffs(h, step + 1),
+                                     b1=f32(h.beta1), b2=f32(h.beta2), eps=f32(h.eps))
         for lo, n in ranges:
             s = slice(lo, lo + n)
             assert float((params[s].double().cpu() - w64[s]).abs().max()) <= 1e-6
@@ -405,7 +331,10 @@ def _simulate_sync(world, clip_norm, steps=XSTEPS, B=XB):
                 1e-6 * float(m64[s].abs().max()) + 1e-30
             assert float((v[s].double().cpu() - v64[s]).abs().max()) <= \
                 1e-6 * float(v64[s].abs().max()) + 1e-30
-    return _canon(params, plan.tensor_offsets).cpu(), pairs
+
+    want = oc.simulate_sync(world, steps, B, oc.dataset_on_card(400, 100), plan,
+                            grad_hook=clipped, after_step=fp64_rule)
+    return want, pairs
 
 
 _NORMS = {}
@@ -426,13 +355,12 @@ def test_xgmi_sync_w2(tmp_path, shard):
     buckets of the contiguous plan): the replicas agree bit for bit and equal the one-process PS
     simulation fed with each rank's own clipped gradient."""
     from conftest import free_port
-    import os
     c = f32(0.5 * min(first_norms(2)))
     want, pairs = _simulate_sync(2, c)
     assert all(p[0][1] < 1.0 for p in pairs)
-    _spawn(_sync_rank, 2, free_port(), str(tmp_path), dict(shard=shard, clip_norm=c))
-    recs = [torch.load(os.path.join(tmp_path, f"rank{r}.pt"), weights_only=False)
-            for r in range(2)]
+    oc.run_ranks(_sync_rank, 2, free_port(), str(tmp_path), dict(shard=shard, clip_norm=c),
+                 limit_s=LIMIT_S)
+    recs = oc.load_ranks(tmp_path, 2)
     print("pairs", [rec["pairs"] for rec in recs], "simulation", pairs)
     assert torch.equal(bits(recs[0]["params"]), bits(recs[1]["params"]))
     for r, rec in enumerate(recs):
@@ -459,66 +387,26 @@ def test_forced_rccl_rehearsal_w1(data):
         tr.train_step(i)
         torch.cuda.synchronize()
         assert same_pair(tuple(tr.clip_out.tolist()), pairs[0][i])
-    got = _canon(tr.params, tr.plan.tensor_offsets).cpu()
+    got = oc.canon(tr.params, tr.plan.tensor_offsets).cpu()
     tr.exchange.close()
     assert torch.equal(bits(got), bits(want))
 
 
 def _async_rank(rank, world, port, outdir, kw):
-    """One rank of a clipped asynchronous run on the xGMI data plane, ASTEPS steps (the set-up of
-    tests/test_async_replay_gpu.py::_rank; W = 1 takes the in-line applies)."""
+    """One rank of a clipped asynchronous run on the xGMI data plane, ASTEPS steps (W = 1 takes
+    the in-line applies)."""
     import os
-    import traceback
-    _env(rank, world, port)
-    try:
-        import torch.distributed as dist
-        from ddl_amd.config import TrainConfig
-        from ddl_amd.parallel.async_xgmi import AsyncPeerExchange
-        from ddl_amd.parallel.comm import init_distributed
-        from ddl_amd.parallel.roles import Trainer
+    with oc.rank_session(rank, world, port) as me:
         from ddl_amd.utils.data import synthetic_mnist
-        env = init_distributed()
-        cfg = TrainConfig(mode="async", steps=ASTEPS, batch_size=XB, eval_every=0, engine="hip",
-                          quiet=True, data_sharding="stride", exchange_backend="xgmi",
-                          check_provenance=True, watchdog_s=120.0, **kw)
-        tr = Trainer(cfg, env, dataset=synthetic_mnist(2000, 500, seed=5))
-        ex = tr.exchange
-        assert isinstance(ex, AsyncPeerExchange) and ex.runner is not None
-        init = tr.params.clone()
-        ex.steps = ASTEPS
-        ex.start()
-        assert ex.inline == (world == 1)
-        if world > 1:
-            torch.cuda.synchronize()
-            dist.barrier()
-        coefs = []
-        for i in range(ASTEPS):
-            tr.train_step(i)
-            torch.cuda.synchronize()
-            coefs.append(float(tr.clip_out[1]))
-        ex.join()
-        ex.verify_provenance()
-        torch.cuda.synchronize()
-        assert ex.peer.error() == 0, ex.peer.error()
-        P = tr.plan.num_ps
-        torch.save({"init": init.cpu(), "params": tr.params.cpu(), "coefs": coefs,
-                    "ps": {p: dict(m=s.m.cpu(), v=s.v.cpu(), t=s.t)
-                           for p, s in tr.servers.items()},
-                    "provenance": list(ex.provenance),
-                    "ranges": [tr.plan.ps_segments(p)[0] for p in range(P)],
-                    "hosts": [tr.plan.host_rank(p, world) for p in range(P)],
-                    "offsets": list(tr.plan.tensor_offsets), "total": tr.plan.total,
-                    "cfg": cfg.to_dict()},
-                   os.path.join(outdir, f"rank{rank}.pt"))
-        if world > 1:
-            dist.barrier()
-        ex.close()
-        if world > 1:
-            dist.barrier()
-            dist.destroy_process_group()
-    except Exception:
-        traceback.print_exc()
-        raise
+        tr = oc.xgmi_trainer(me.env, "async", ASTEPS, XB, synthetic_mnist(2000, 500, seed=5), **kw)
+        assert tr.exchange.runner is not None
+
+        def started(ex):
+            assert ex.inline == (world == 1)
+
+        rec = oc.async_rank_record(tr, world, ASTEPS, per_step=_pairs, after_start=started)
+        torch.save(rec, os.path.join(outdir, f"rank{rank}.pt"))
+        me.close_single(tr.exchange)
 
 
 @pytest.mark.slow
@@ -529,56 +417,22 @@ def _async_rank(rank, world, port, outdir, kw):
 def test_xgmi_async_equals_its_replay(tmp_path, world, kw):
     """Async over xGMI, W = 1 in-line applies and W = 2 on the arrival board: the run equals the
     replay of its recorded apply orders with a gradient function that clips, bit for bit."""
-    import os
     import async_replay as ar
     from conftest import free_port
-    from ddl_amd.models.hip_engine import HipEngine
-    from ddl_amd.ops import rng
-    from ddl_amd.ops.adam import AdamHyper, adam_coeffs
-    from ddl_amd.utils.data import batch_indices, synthetic_mnist
     c = 0.75   # below the first steps' norms at this batch (asserted through the coefficients)
-    _spawn(_async_rank, world, free_port(), str(tmp_path), dict(kw, clip_norm=c))
-    recs = [torch.load(os.path.join(tmp_path, f"rank{r}.pt"), weights_only=False)
-            for r in range(world)]
-    hosts, ranges = recs[0]["hosts"], recs[0]["ranges"]
-    order = ar.apply_orders([e for rec in recs for e in rec["provenance"]], world, ASTEPS)
+    oc.run_ranks(_async_rank, world, free_port(), str(tmp_path), dict(kw, clip_norm=c),
+                 limit_s=LIMIT_S)
+    recs = oc.load_ranks(tmp_path, world)
+    _, order = oc.recorded_orders(recs, world, ASTEPS)
     print("orders", {p: ar.order_string(o) for p, o in order.items()},
           "coefs", [rec["coefs"] for rec in recs])
     assert all(min(rec["coefs"]) < 1.0 for rec in recs)
-    cfg = recs[0]["cfg"]
-    data = synthetic_mnist(2000, 500, seed=5).to(DEV)
-    params = torch.zeros(recs[0]["total"], device=DEV)
-    grads = torch.zeros_like(params)
-    eng = HipEngine(params, grads, recs[0]["offsets"], batch=XB, graph=False, eval_chunk=XB)
     table = C.payload_ranges(recs[0]["offsets"])
     out = torch.zeros(2, dtype=torch.float32, device=DEV)
-    h = AdamHyper(lr=f32(cfg["lr"]), beta1=f32(0.9), beta2=f32(0.999))
-    ops = native.ops()
 
-    def grad_fn(r, s, params_r):
-        params.copy_(params_r)
-        lo, hi = batch_indices(s, XB, data.total_batch, r, world, cfg["data_sharding"])
-        eng.forward_backward(data.x_train[lo:hi], data.y_train[lo:hi], cfg["keep_prob"],
-                             rng.step_seed(cfg["seed"], r, s))
-        ops.clip_grads(grads, table, c, out)
-        return grads.clone()
+    def clipped(ge, r, s):
+        oc.plain_grad(ge, r, s)
+        native.ops().clip_grads(ge.grads, table, c, out)
 
-    def update_fn(p, st, g, t):
-        ops.update_flat(ADAM_K, st.w, g, st.m, st.v, adam_coeffs(h, t), 0.9, 0.999, 1e-8, 0.0, 1.0)
-
-    want, state = ar.replay(order, ranges, recs[0]["init"].to(DEV), world, ASTEPS, grad_fn,
-                            update_fn)
-    torch.cuda.synchronize()
-    for r in range(world):
-        for lo, n in table:
-            assert torch.equal(bits(recs[r]["params"][lo:lo + n]), bits(want[r][lo:lo + n])), r
-    for p in range(len(hosts)):
-        got = recs[hosts[p]]["ps"][p]
-        w, m, v, t = state[p]
-        assert got["t"] == t
-        lo0 = ranges[p][0]
-        for lo, n in table:
-            a, b = max(lo, ranges[p][0]) - lo0, min(lo + n, ranges[p][1]) - lo0
-            if a < b:
-                assert torch.equal(bits(got["m"][a:b]), bits(m[a:b]))
-                assert torch.equal(bits(got["v"][a:b]), bits(v[a:b]))
+    want, state = oc.replay_async(recs, world, order, ASTEPS, grad_hook=clipped)
+    oc.assert_payload_equals_replay(recs, world, want, state, table)

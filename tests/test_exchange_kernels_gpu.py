@@ -23,14 +23,14 @@ launches several buckets in index order on one stream, the replicated bucket las
 on the last launch, with no host barrier between the rounds: the parity-slot and inbox reuse
 argument of xgmi.hip's header is what runs.  Measured: see docs/DESIGN.md."""
 import os
-import sys
 import time
-import traceback
 
 import pytest
 import torch
 
-from conftest import ROOT, free_port
+import onecard as oc
+from conftest import free_port
+from onecard import rel_err as _rel
 
 import exchange_reference as xr
 from exchange_reference import ADAM, MOMENTUM, COPY, B1, B2, EPS
@@ -47,11 +47,6 @@ THIRD = xr.COEF3
 def _snap(t):
     """A host copy that shares nothing with the device buffer."""
     return t.detach().cpu().clone()
-
-
-def _rel(a, b):
-    a, b = a.double(), b.double()
-    return float((a - b).abs().max() / (b.abs().max() + 1e-30))
 
 
 # ---- plans ---------------------------------------------------------------------------------------
@@ -245,10 +240,8 @@ def run_sync_cell(ops, rank, world, cell, rule, gather, fails, integer=False):
             fails.check(all(torch.equal(s[e], got[0][1][e]) for _, s in got),
                         f"round {e + 1}: the ranks' parameter replicas differ")
         err = max(x for x, _ in got)
-        # HIP leaves freeing an exported buffer undefined while a peer still has it mapped, and
-        # this process goes on to build the next cell's exchange: every rank unmaps its peers'
-        # buffers, a barrier, then every rank frees its own, a barrier.  (Without them a wait of
-        # a later cell timed out once in two runs: the peer's flag stores never showed.)
+        # unmap, barrier, free, barrier: this process goes on to build the next cell's exchange
+        # (why: tests/onecard.py, close_one_of_several)
         ex.unmap_peers()
         gather(None)
         ex.close()
@@ -495,17 +488,10 @@ ASYNC_W3 = dict(sizes=[4, 2052, 4100, 2044], hosts=[0, 2, 2, 1])
 
 
 def _job(rank, world, port, outdir):
-    if ROOT not in sys.path:
-        sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
-                      WORLD_SIZE=str(world), LOCAL_RANK=str(rank), DDL_DIST_BACKEND="gloo",
-                      DDL_XGMI_TIMEOUT_S="10")
-    try:
-        import torch.distributed as dist
+    with oc.rank_session(rank, world, port, xgmi_timeout_s="10", on_device_0=True) as me:
         from ddl_amd.ops import native
-        from ddl_amd.parallel.comm import init_distributed
-        env = init_distributed()
-        assert env.device.index == 0 and native.available(), native.error()
+        dist = me.dist
+        assert native.available(), native.error()
         ops = native.ops()
 
         def gather(x):
@@ -539,22 +525,15 @@ def _job(rank, world, port, outdir):
         torch.cuda.synchronize()
         torch.save({"fails": list(fails), "times": times, "stopped": stopped},
                    os.path.join(outdir, f"rank{rank}.pt"))
-        dist.barrier()
-        dist.destroy_process_group()
-    except Exception:
-        traceback.print_exc()
-        raise
 
 
 @pytest.mark.slow
 @pytest.mark.parametrize("world", [2, 3])
 def test_exchange_kernels_multiprocess(tmp_path, world):
-    import torch.multiprocessing as mp
     t = time.perf_counter()
-    mp.spawn(_job, args=(world, free_port(), str(tmp_path)), nprocs=world, join=True)
+    oc.run_ranks(_job, world, free_port(), str(tmp_path), limit_s=oc.LIMIT_S)
     wall = time.perf_counter() - t
-    recs = [torch.load(os.path.join(tmp_path, f"rank{r}.pt"), weights_only=False)
-            for r in range(world)]
+    recs = oc.load_ranks(tmp_path, world)
     cells = sum(recs[0]["times"].values())
     print(f"W={world}: job {wall:.1f} s, of which {len(recs[0]['times'])} cells {cells:.2f} s")
     fails = [f"rank {r}: {f}" for r, rec in enumerate(recs) for f in rec["fails"]]

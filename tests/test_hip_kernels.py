@@ -12,15 +12,12 @@ from ddl_amd.models.layout import TENSORS, CANON_OFFSETS, TOTAL_NUMEL
 from ddl_amd.models.mnist_cnn import (init_params_, param_views, torch_forward, xent_loss,
                                       dropout_apply, _pool_same)
 from ddl_amd.ops import rng
+from onecard import rel_err
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 
-
-def rel_err(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return float((a - b).abs().max() / (b.abs().max() + 1e-30))
 
 
 def ref_intermediates(p, x, keep, seed):

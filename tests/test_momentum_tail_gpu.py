@@ -5,22 +5,16 @@ momentum1 (common.h) pins the roundings, so every placement must give the same b
 import pytest
 import torch
 
-from ddl_amd.config import TrainConfig
-from ddl_amd.parallel.comm import DistEnv
-from ddl_amd.parallel.roles import Trainer
 from ddl_amd.utils.data import synthetic_mnist
 
 from momentum_reference import momentum_closed_form
+from onecard import PLACEMENTS, placement_run, rel_err
+from onecard import assert_same_run as _assert_same
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 GUARD = 8  # NaN elements on either side of a shard (a multiple of 4: keeps the shard 16-B aligned)
-
-
-def rel_err(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return float((a - b).abs().max() / (b.abs().max() + 1e-30))
 
 
 def _guarded(x, shift):
@@ -80,46 +74,10 @@ def data():
 STEPS = 5
 
 
-def _trainer(data, optimizer, shard, seed=0):
-    env = DistEnv(0, 1, 0, torch.device("cuda", 0))
-    cfg = TrainConfig(mode="sync", shard=shard, steps=STEPS, batch_size=100, eval_every=0,
-                      engine="hip", quiet=True, optimizer=optimizer, lr=1e-2, seed=seed)
-    return Trainer(cfg, env, dataset=data)
-
-
 def _run(data, optimizer, shard, tail=None, final=None, setup=None, seed=0):
-    """Parameters and every server's (m, v) after STEPS steps, and update_launches() of the
-    last one.  tail / final None: the runner's default."""
-    tr = _trainer(data, optimizer, shard, seed)
-    if tail is not None:
-        tr.exchange.runner.set_use_tail(tail)
-    if final is not None:
-        tr.exchange.runner.set_final_in_reduce(final)
-    if setup is not None:
-        setup(tr)
-    p0 = tr.params.clone()
-    for i in range(STEPS):
-        tr.train_step(i)
-    torch.cuda.synchronize()
-    assert not torch.equal(tr.params, p0)  # it trained
-    state = [(s.m.clone(), s.v) for _, s in sorted(tr.servers.items())]
-    return tr.params.clone(), state, tr.exchange.runner.update_launches()
-
-
-def _assert_same(a, b, has_v):
-    (pa, sa, _), (pb, sb, _) = a, b
-    assert torch.isfinite(pa).all()
-    assert torch.equal(pa, pb)
-    assert len(sa) == len(sb) > 0
-    for (ma, va), (mb, vb) in zip(sa, sb):
-        assert torch.equal(ma, mb)
-        if has_v:
-            assert torch.equal(va, vb)
-        else:
-            assert va is None and vb is None
-
-
-PLACEMENTS = ((True, True), (True, False), (False, False))  # (set_use_tail, set_final_in_reduce)
+    """onecard.placement_run at STEPS steps of batch 100."""
+    return placement_run(data, dict(optimizer=optimizer), shard, STEPS, 100, tail, final, setup,
+                         seed)
 
 
 @pytest.mark.parametrize("shard", ["flat", "contiguous"])

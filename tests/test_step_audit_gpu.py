@@ -80,6 +80,7 @@ from ddl_amd.ops.adam import adam_coeffs
 from ddl_amd.parallel.comm import DistEnv
 from ddl_amd.parallel.roles import Trainer
 from ddl_amd.utils.data import synthetic_mnist
+from onecard import f32, rel_err
 from oracle_common import (BATCHES, BMAX, CODE_BUFS, DEV, FLOAT_BUFS, HALO_BUFS, bits, interior,
                            make_real_params, prepare, untouched_failures)
 
@@ -273,14 +274,6 @@ def untouched(ctx, B, snap, bufs, tag):
         fails.append(f"{tag}: gradient padding written")
     return fails
 
-
-def rel_err(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return float((a - b).abs().max() / (b.abs().max() + 1e-30))
-
-
-def f32(x):
-    return float(torch.tensor(x, dtype=torch.float32))
 
 
 def stored_hyper(h):

@@ -16,6 +16,7 @@ import async_replay as ar
 import test_async_replay_cpu as replay_cells
 from conftest import free_port
 from dist_helpers import spawn, train_rank
+from onecard import rel_err
 from update_rule_reference import update_closed_form
 
 from ddl_amd.ops.adam import AdamHyper
@@ -91,11 +92,6 @@ VARIANTS = [
     pytest.param("sgd", 3e-2, 0.0, WD, False, id="sgd-wd"),
 ]
 
-
-def rel_err(a, b):
-    """The project's relative error (tests/test_hip_kernels.py): against the largest element."""
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return float((a - b).abs().max() / (b.abs().max() + 1e-30))
 
 
 def check_step(tag, got, before, g, kind, lr, mu, wd, nesterov, scale, t0):

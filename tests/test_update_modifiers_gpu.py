@@ -18,15 +18,16 @@ Measured on one MI355X: the two spawned jobs 2.7 and 3.2 s (nearly all of it the
 every other case under 0.5 s; against the closed form |w - ref| <= 2.3e-7, rel m <= 2.4e-7, rel v <= 1.9e-7
 (bounds 1e-6)."""
 import os
-import sys
-import time
-import traceback
 
 import pytest
 import torch
 
 import async_replay as ar
-from conftest import ROOT, free_port
+import onecard as oc
+from conftest import free_port
+from onecard import PLACEMENTS, f32, rel_err
+from onecard import assert_same_run as _assert_same
+from oracle_common import bits
 from update_rule_reference import adam_step_size, update_closed_form
 
 pytestmark = pytest.mark.gpu
@@ -40,15 +41,6 @@ STEPS = 3
 ADAMW = dict(optimizer="adam", weight_decay=WD)
 NESTEROV_WD = dict(optimizer="momentum", nesterov=True, weight_decay=WD)
 JOB_LIMIT_S = 150.0
-
-
-def rel_err(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return float((a - b).abs().max() / (b.abs().max() + 1e-30))
-
-
-def bits(t):
-    return t.detach().contiguous().view(torch.int32)
 
 
 # ---- 1. the stand-alone shapes -------------------------------------------------------------------
@@ -233,47 +225,8 @@ def data():
 
 
 def _run(data, opts, shard, tail=None, final=None, setup=None):
-    """Parameters and every server's (m, v) after STEPS steps, and update_launches() of the last
-    one.  tail / final None: the runner's default."""
-    from ddl_amd.config import TrainConfig
-    from ddl_amd.parallel.comm import DistEnv
-    from ddl_amd.parallel.roles import Trainer
-    env = DistEnv(0, 1, 0, torch.device("cuda", 0))
-    cfg = TrainConfig(mode="sync", shard=shard, steps=STEPS, batch_size=BATCH, eval_every=0,
-                      engine="hip", quiet=True, lr=1e-2, seed=0, **opts)
-    tr = Trainer(cfg, env, dataset=data)
-    runner = tr.exchange.runner
-    if tail is not None:
-        runner.set_use_tail(tail)
-    if final is not None:
-        runner.set_final_in_reduce(final)
-    if setup is not None:
-        setup(tr)
-    p0 = tr.params.clone()
-    for i in range(STEPS):
-        tr.train_step(i)
-    torch.cuda.synchronize()
-    assert not torch.equal(tr.params, p0)  # it trained
-    state = [(s.m.clone(), None if s.v is None else s.v.clone())
-             for _, s in sorted(tr.servers.items())]
-    out = tr.params.clone(), state, runner.update_launches()
-    tr.exchange.close()
-    return out
-
-
-def _assert_same(a, b):
-    (pa, sa, _), (pb, sb, _) = a, b
-    assert torch.isfinite(pa).all()
-    assert torch.equal(bits(pa), bits(pb))
-    assert len(sa) == len(sb) > 0
-    for (ma, va), (mb, vb) in zip(sa, sb):
-        assert torch.equal(bits(ma), bits(mb))
-        assert (va is None) == (vb is None)
-        if va is not None:
-            assert torch.equal(bits(va), bits(vb))
-
-
-PLACEMENTS = ((True, True), (True, False), (False, False))  # (set_use_tail, set_final_in_reduce)
+    """onecard.placement_run at STEPS steps of BATCH."""
+    return oc.placement_run(data, opts, shard, STEPS, BATCH, tail, final, setup)
 
 
 @pytest.mark.parametrize("shard", ["flat", "contiguous"])
@@ -312,10 +265,6 @@ def test_other_engine_paths(data, setting):
 
 
 # ---- 4. the asynchronous W = 1 step with in-line applies --------------------------------------------
-def f32(x):
-    return float(torch.tensor(x, dtype=torch.float32))
-
-
 def test_async_inline_adamw(data, monkeypatch):
     """--mode async --exchange xgmi at one worker: each PS's AdamW as tail blocks of the next
     segment's launch.  No suite demands the bits of the synchronous run of this path (the step
@@ -370,130 +319,58 @@ def test_async_inline_adamw(data, monkeypatch):
 
 
 # ---- 5. the exchange kernels: W = 2 on one card -----------------------------------------------------
-def _spawn(fn, world, *args):
-    """fn(rank, world, *args) in `world` fresh processes under one time limit for the job."""
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    kids = [ctx.Process(target=fn, args=(r, world, *args)) for r in range(world)]
-    for k in kids:
-        k.start()
-    deadline = time.monotonic() + JOB_LIMIT_S
-    for k in kids:
-        k.join(timeout=max(0.0, deadline - time.monotonic()))
-    late = [k for k in kids if k.is_alive()]
-    for k in late:
-        k.kill()
-        k.join()
-    assert not late, f"{len(late)} rank(s) still running after {JOB_LIMIT_S:.0f} s"
-    assert all(k.exitcode == 0 for k in kids), [k.exitcode for k in kids]
-
-
-def _enter(rank, world, port):
-    if ROOT not in sys.path:
-        sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
-                      WORLD_SIZE=str(world), LOCAL_RANK=str(rank), DDL_DIST_BACKEND="gloo",
-                      DDL_XGMI_TIMEOUT_S="20", DDL_ASYNC_INLINE="0")
-
-
-def _canon(params, offsets):
-    from ddl_amd.models.layout import TENSORS
-    return torch.cat([params[offsets[t.index]:offsets[t.index] + t.numel] for t in TENSORS])
-
-
+JOB_ENV = dict(DDL_ASYNC_INLINE="0")
 SYNC_CELLS = [(shard, name, opts) for shard in ("flat", "contiguous")  # contiguous: owner buckets
               for name, opts in (("adamw", ADAMW), ("nesterov-wd", NESTEROV_WD))]
 ASYNC_CELLS = [("adamw", ADAMW), ("nesterov-wd", NESTEROV_WD)]
 
 
 def _sync_job(rank, world, port, outdir):
-    _enter(rank, world, port)
-    try:
-        import torch.distributed as dist
-        from ddl_amd.config import TrainConfig
-        from ddl_amd.parallel.comm import init_distributed
-        from ddl_amd.parallel.roles import Trainer
+    with oc.rank_session(rank, world, port, env=JOB_ENV, on_device_0=True) as me:
         from ddl_amd.utils.data import synthetic_mnist
-        env = init_distributed()
-        assert env.device.index == 0
         data = synthetic_mnist(2000, 500, seed=5)
         out = {}
         for shard, name, opts in SYNC_CELLS:
-            cfg = TrainConfig(mode="sync", shard=shard, steps=STEPS, batch_size=BATCH,
-                              eval_every=0, engine="hip", quiet=True, data_sharding="stride",
-                              exchange_backend="xgmi", **opts)
-            tr = Trainer(cfg, env, dataset=data)
+            tr = oc.xgmi_trainer(me.env, "sync", STEPS, BATCH, data, shard=shard, **opts)
             ex = tr.exchange
-            assert getattr(ex, "native", False) and ex.peer is not None, "xgmi path not taken"
             owner = shard != "flat"
             assert all((ex.peer.owner(b) >= 0) == owner for b in range(len(ex.peer.nslices())))
-            for i in range(STEPS):
-                tr.train_step(i)
-            torch.cuda.synchronize()
-            ex.check()
+            rec = oc.sync_rank_record(tr, STEPS)
             assert ex.peer.error() == 0, ex.peer.error()
-            out[(shard, name)] = dict(params=_canon(tr.params, tr.plan.tensor_offsets).cpu(),
-                                      t={p: s.t for p, s in tr.servers.items()})
-            # unmap, barrier, close, barrier: no rank frees a buffer a peer still has mapped
-            dist.barrier()
-            ex.runner.close()
-            ex.peer.unmap_peers()
-            dist.barrier()
-            ex.peer.close()
-            dist.barrier()
+            out[(shard, name)] = dict(params=rec["params"], t=rec["t"])
+            me.close_one_of_several(ex)
             del tr, ex
         torch.save(out, os.path.join(outdir, f"rank{rank}.pt"))
-        dist.barrier()
-        dist.destroy_process_group()
-    except Exception:
-        traceback.print_exc()
-        raise
 
 
 def _simulate_sync(world, opts):
-    """One process: every rank's gradient on its own batch and dropout seed, summed in rank order
-    (the kernels' order), one update_flat with the options per global step."""
+    """onecard.simulate_sync with one update_flat with the options per global step."""
     from ddl_amd.models import engine_segments
-    from ddl_amd.models.hip_engine import HipEngine
-    from ddl_amd.models.mnist_cnn import init_params_
-    from ddl_amd.ops import native, rng
+    from ddl_amd.ops import native
     from ddl_amd.ops.adam import AdamHyper, adam_coeffs
     from ddl_amd.parallel.sharding import make_plan
-    from ddl_amd.utils.data import synthetic_mnist, batch_indices
-    dev = torch.device("cuda", 0)
-    data = synthetic_mnist(2000, 500, seed=5).to(dev)
-    plan = make_plan("flat", world, buckets=engine_segments("hip", dev))
-    params = torch.zeros(plan.total, device=dev)
-    init_params_(params, plan.tensor_offsets, 0)
-    grads = torch.zeros_like(params)
-    acc, m, v = torch.zeros_like(params), torch.zeros_like(params), torch.zeros_like(params)
-    eng = HipEngine(params, grads, plan.tensor_offsets, batch=BATCH, graph=False, eval_chunk=BATCH)
+    plan = make_plan("flat", world, buckets=engine_segments("hip", torch.device("cuda", 0)))
     h = AdamHyper()
     adam = opts["optimizer"] == "adam"
     decay = h.lr * opts.get("weight_decay", 0.0)
-    for step in range(STEPS):
-        acc.zero_()
-        for r in range(world):
-            lo, hi = batch_indices(step, BATCH, data.total_batch, r, world, "stride")
-            eng.forward_backward(data.x_train[lo:hi], data.y_train[lo:hi], 0.5,
-                                 rng.step_seed(0, r, step))
-            acc.add_(grads)
+
+    def update(params, acc, m, v, step):
         if adam:
             native.ops().update_flat(ADAM, params, acc, m, v, adam_coeffs(h, step + 1), h.beta1,
                                      h.beta2, h.eps, 0.0, 1.0, decay, False)
         else:
             native.ops().update_flat(MOMENTUM, params, acc, m, None, h.lr, 0.0, 0.0, 0.0, MU, 1.0,
                                      decay, bool(opts.get("nesterov", False)))
-    torch.cuda.synchronize()
-    return _canon(params, plan.tensor_offsets).cpu()
+
+    return oc.simulate_sync(world, STEPS, BATCH, oc.dataset_on_card(2000, 500), plan,
+                            update=update)
 
 
 @pytest.mark.slow
 def test_xgmi_sync_exchange_with_options(tmp_path):
     world = 2
-    _spawn(_sync_job, world, free_port(), str(tmp_path))
-    recs = [torch.load(os.path.join(tmp_path, f"rank{r}.pt"), weights_only=False)
-            for r in range(world)]
+    oc.run_ranks(_sync_job, world, free_port(), str(tmp_path), limit_s=JOB_LIMIT_S)
+    recs = oc.load_ranks(tmp_path, world)
     sims = {}
     for shard, name, opts in SYNC_CELLS:
         a, b = recs[0][(shard, name)], recs[1][(shard, name)]
@@ -509,135 +386,57 @@ def test_xgmi_sync_exchange_with_options(tmp_path):
 
 
 def _async_job(rank, world, port, outdir):
-    _enter(rank, world, port)
-    try:
-        import torch.distributed as dist
-        from ddl_amd.config import TrainConfig
-        from ddl_amd.parallel.async_xgmi import AsyncPeerExchange
-        from ddl_amd.parallel.comm import init_distributed
-        from ddl_amd.parallel.roles import Trainer
+    with oc.rank_session(rank, world, port, env=JOB_ENV, on_device_0=True) as me:
         from ddl_amd.utils.data import synthetic_mnist
-        env = init_distributed()
-        assert env.device.index == 0
         data = synthetic_mnist(2000, 500, seed=5)
         out = {}
-        for name, opts in ASYNC_CELLS:
-            cfg = TrainConfig(mode="async", shard="contiguous", steps=STEPS, batch_size=BATCH,
-                              eval_every=0, engine="hip", quiet=True, data_sharding="stride",
-                              exchange_backend="xgmi", check_provenance=True, watchdog_s=120.0,
-                              **opts)
-            tr = Trainer(cfg, env, dataset=data)
-            ex = tr.exchange
-            assert isinstance(ex, AsyncPeerExchange) and ex.runner is not None
-            init = tr.params.clone()
-            ex.steps = STEPS
-            ex.start()
+
+        def started(ex):
             assert ex.service_mode == "host", ex.service_mode  # the board service
-            torch.cuda.synchronize()
-            dist.barrier()  # the ranks start together: their pushes do meet at the PS
-            for i in range(STEPS):
-                tr.train_step(i)
-            ex.join()
-            ex.verify_provenance()
-            torch.cuda.synchronize()
-            assert ex.peer.error() == 0, ex.peer.error()
-            P = tr.plan.num_ps
-            out[name] = {"init": init.cpu(), "params": tr.params.cpu(),
-                         "ps": {p: dict(w=s.params.cpu(), m=s.m.cpu(),
-                                        v=None if s.v is None else s.v.cpu(), t=s.t)
-                                for p, s in tr.servers.items()},
-                         "provenance": list(ex.provenance),
-                         "ranges": [tr.plan.ps_segments(p)[0] for p in range(P)],
-                         "hosts": [tr.plan.host_rank(p, world) for p in range(P)],
-                         "offsets": list(tr.plan.tensor_offsets), "total": tr.plan.total,
-                         "cfg": cfg.to_dict()}
-            dist.barrier()
-            ex.peer.unmap_peers()
-            dist.barrier()
-            ex.close()
-            dist.barrier()
+
+        for name, opts in ASYNC_CELLS:
+            tr = oc.xgmi_trainer(me.env, "async", STEPS, BATCH, data, shard="contiguous", **opts)
+            ex = tr.exchange
+            assert ex.runner is not None
+            out[name] = oc.async_rank_record(tr, world, STEPS, after_start=started)
+            me.close_one_of_several(ex)
             del tr, ex
         torch.save(out, os.path.join(outdir, f"rank{rank}.pt"))
-        dist.barrier()
-        dist.destroy_process_group()
-    except Exception:
-        traceback.print_exc()
-        raise
 
 
 def _replay_async(recs, world, order, with_options):
-    """The run again in this process in the recorded order: the engine's gradients and
-    ops.update_flat, with or without the run's options."""
-    from ddl_amd.models.hip_engine import HipEngine
-    from ddl_amd.ops import native, rng
-    from ddl_amd.ops.adam import AdamHyper, adam_coeffs
-    from ddl_amd.utils.data import batch_indices, synthetic_mnist
-    dev = torch.device("cuda", 0)
-    cfg = recs[0]["cfg"]
-    data = synthetic_mnist(2000, 500, seed=5).to(dev)
-    params = torch.zeros(recs[0]["total"], device=dev)
-    grads = torch.zeros_like(params)
-    eng = HipEngine(params, grads, recs[0]["offsets"], batch=BATCH, graph=False, eval_chunk=BATCH)
-    # the service holds lr and the betas as float32 and widens them for Adam's step size; the
-    # decay is formed from the doubles (update.h upd_decay)
-    h = AdamHyper(lr=f32(cfg["lr"]), beta1=f32(0.9), beta2=f32(0.999))
-    adam = cfg["optimizer"] == "adam"
-    decay = cfg["lr"] * cfg["weight_decay"] if with_options else 0.0
-    nesterov = bool(cfg["nesterov"]) and with_options
+    """onecard.replay_async with or without the run's options."""
+    from ddl_amd.ops import native
+    from ddl_amd.ops.adam import adam_coeffs
 
-    def grad_fn(r, s, params_r):
-        params.copy_(params_r)
-        lo, hi = batch_indices(s, BATCH, data.total_batch, r, world, cfg["data_sharding"])
-        eng.forward_backward(data.x_train[lo:hi], data.y_train[lo:hi], cfg["keep_prob"],
-                             rng.step_seed(cfg["seed"], r, s))
-        return grads.clone()
-
-    def update_fn(p, st, g, t):
-        if adam:
+    def update(st, g, t, h, cfg):
+        decay = cfg["lr"] * cfg["weight_decay"] if with_options else 0.0
+        if cfg["optimizer"] == "adam":
             native.ops().update_flat(ADAM, st.w, g, st.m, st.v, adam_coeffs(h, t), 0.9, 0.999,
                                      1e-8, 0.0, 1.0, decay, False)
         else:
             native.ops().update_flat(MOMENTUM, st.w, g, st.m, None, f32(cfg["lr"]), 0.0, 0.0, 0.0,
-                                     cfg["momentum"], 1.0, decay, nesterov)
+                                     cfg["momentum"], 1.0, decay,
+                                     bool(cfg["nesterov"]) and with_options)
 
-    out = ar.replay(order, recs[0]["ranges"], recs[0]["init"].to(dev), world, STEPS, grad_fn,
-                    update_fn)
-    torch.cuda.synchronize()
-    return out
+    return oc.replay_async(recs, world, order, STEPS, update=update)
 
 
 @pytest.mark.slow
 def test_xgmi_async_service_with_options(tmp_path):
     world = 2
-    _spawn(_async_job, world, free_port(), str(tmp_path))
-    jobs = [torch.load(os.path.join(tmp_path, f"rank{r}.pt"), weights_only=False)
-            for r in range(world)]
+    oc.run_ranks(_async_job, world, free_port(), str(tmp_path), limit_s=JOB_LIMIT_S)
+    jobs = oc.load_ranks(tmp_path, world)
     for name, _ in ASYNC_CELLS:
         recs = [j[name] for j in jobs]
-        hosts, ranges = recs[0]["hosts"], recs[0]["ranges"]
         assert torch.equal(recs[0]["init"], recs[1]["init"])
-        log = [e for rec in recs for e in rec["provenance"]]
-        assert len(log) == len(hosts) * world * STEPS  # the xGMI service logs every apply
-        order = ar.apply_orders(log, world, STEPS)
+        _, order = oc.recorded_orders(recs, world, STEPS)
         print(f"{name}: orders", {p: ar.order_string(o) for p, o in order.items()})
         params, state = _replay_async(recs, world, order, True)
-        fails = []
-        spans = [(lo, hi, f"range of PS {p}") for p, (lo, hi) in enumerate(ranges)]
-        for r in range(world):
-            fails += ar.mismatch_report(f"{name} worker {r}", recs[r]["params"], params[r].cpu(),
-                                        spans)
-            if not torch.equal(bits(recs[r]["params"]), bits(params[r].cpu())):
-                fails.append(f"{name} worker {r}: buffer differs from the replay")
-        for p in range(len(hosts)):
-            got = recs[hosts[p]]["ps"][p]
-            w, m, v, t = state[p]
-            if got["t"] != t or t != world * STEPS:
-                fails.append(f"{name} PS {p}: t {got['t']}, replay {t}")
-            for what, a, b in (("params", got["w"], w), ("m", got["m"], m), ("v", got["v"], v)):
-                if a is None:
-                    assert what == "v" and recs[0]["cfg"]["optimizer"] != "adam"
-                elif not torch.equal(bits(a), bits(b.cpu())):
-                    fails.append(f"{name} PS {p} {what}: differs from the replay")
+        spans = [(lo, hi, f"PS {p} / its range") for p, (lo, hi) in enumerate(recs[0]["ranges"])]
+        fails = oc.replay_mismatches(recs, world, params, state, spans, tag=f"{name} ")
+        fails += [f"{name} PS {p}: t {t}, not {world * STEPS}" for p, (_, _, _, t) in state.items()
+                  if t != world * STEPS]
         assert not fails, "\n".join(fails[:30])
         plain, _ = _replay_async(recs, world, order, False)
         moved = max(float((a - b).abs().max()) for a, b in zip(plain, params))

@@ -11,143 +11,69 @@ simulation of the PS math with the same HIP engine: each rank's gradient on its 
 dropout seed, summed in rank order (the kernel's order), one TF1 Adam step per global step.
 """
 import os
-import sys
-import traceback
 
 import pytest
 import torch
 
-from conftest import ROOT, free_port
+import onecard as oc
+from conftest import free_port
 
 pytestmark = [pytest.mark.gpu, pytest.mark.slow]
 
 STEPS = 4
 
-
-def _canon(params, offsets):
-    from ddl_amd.models.layout import TENSORS
-    return torch.cat([params[offsets[t.index]:offsets[t.index] + t.numel] for t in TENSORS])
-
-
 # Eight processes on ONE card: each pinned to one hardware queue (GPU_MAX_HW_QUEUES=1, HIP
 # reads it at init), so the box runs 8 queues, not 8 x 4 (the oversubscribed regime round 2's
 # W = 8 runs stalled in), and with the inbox checksums on (DDL_XGMI_CHECK=1: every owner
 # verifies every pushed slice against its pusher's checksum, error code 3 on a mismatch).
+# Rank 0 of a W = 8 job is this process (onecard.run_ranks, rank0_here).
 W8_ENV = dict(GPU_MAX_HW_QUEUES="1", DDL_XGMI_CHECK="1", DDL_XGMI_TIMEOUT_S="60")
-# W = 8 on one card runs with EXACTLY eight GPU processes: rank 0 is this pytest process
-# (which already holds a GPU context from the earlier tests) and ranks 1..7 are spawned.  The
-# round-3 abort (HSA_STATUS_ERROR_ILLEGAL_INSTRUCTION in a GEMM dual kernel,
-# profiles/r3_w8_one_gpu_fault.log) happened with mp.spawn's eight ranks PLUS this process — nine
-# processes with hardware queues, one more than the eight compute VMIDs the kernel driver's
-# scheduler keeps resident at once, so the run list was over-subscribed and the scheduler
-# time-sliced whole processes by preempting their waves (context save / restore) — the regime
-# every W = 8 stall, divergence and abort on one card was seen in, and one no 8-GPU node (one
-# process per GPU) ever enters.  docs/DESIGN.md "W = 8 on one card: the cause".
-def _inproc_rank0(fn, world, *args):
-    """fn(rank, world, *args) on ranks 1..world-1 in spawned processes and rank 0 here."""
-    import gc
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    kids = [ctx.Process(target=fn, args=(r, world, *args)) for r in range(1, world)]
-    for k in kids:
-        k.start()
-    saved = dict(os.environ)
-    ok = False
-    try:
-        fn(0, world, *args)
-        ok = True
-    finally:
-        os.environ.clear()
-        os.environ.update(saved)
-        for k in kids:
-            k.join(timeout=180 if ok else 5)
-            if k.is_alive():
-                k.kill()
-                k.join()
-        gc.collect()
-        torch.cuda.synchronize()
-    assert all(k.exitcode == 0 for k in kids), [k.exitcode for k in kids]
+
+
+def _job(fn, world, *args):
+    if world == 8:
+        oc.run_ranks(fn, world, *args, limit_s=oc.W8_LIMIT_S, rank0_here=True)
+    else:
+        oc.run_ranks(fn, world, *args, limit_s=oc.LIMIT_S)
+
+
+def _data(n_train=2000):
+    from ddl_amd.utils.data import synthetic_mnist
+    return synthetic_mnist(n_train, 500, seed=5)
+
+
+def _checksum(params, offsets):
+    return oc.canon(params, offsets).double().sum().item()
 
 
 def _rank(rank, world, port, outdir, kw):
-    if ROOT not in sys.path:
-        sys.path.insert(0, ROOT)
     kw = dict(kw)
     extra_env = kw.pop("_env", {})
     kw.pop("_ps", None)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
-                      WORLD_SIZE=str(world), LOCAL_RANK=str(rank), DDL_DIST_BACKEND="gloo",
-                      DDL_XGMI_TIMEOUT_S="20")
-    os.environ.update(extra_env)
-    try:
-        import torch.distributed as dist
-        from ddl_amd.config import TrainConfig
-        from ddl_amd.parallel.comm import init_distributed
-        from ddl_amd.parallel.roles import Trainer
-        from ddl_amd.utils.data import synthetic_mnist
-        env = init_distributed()
-        assert env.device.index == 0
+    with oc.rank_session(rank, world, port, env=extra_env, on_device_0=True) as me:
         shard = kw.pop("shard", "flat")
-        cfg = TrainConfig(mode="sync", shard=shard, steps=STEPS, batch_size=100, eval_every=0,
-                          engine="hip", quiet=True, data_sharding="stride",
-                          exchange_backend="xgmi", **kw)
-        tr = Trainer(cfg, env, dataset=synthetic_mnist(2000, 500, seed=5))
+        tr = oc.xgmi_trainer(me.env, "sync", STEPS, 100, _data(), shard=shard, **kw)
         ex = tr.exchange
-        assert getattr(ex, "native", False) and ex.peer is not None, "xgmi path not taken"
         # tensor-granular plans: one xGMI OWNER bucket per exchange unit, hosted where its PS is
         owner = shard != "flat" or tr.plan.num_ps != world
         assert all((ex.peer.owner(b) >= 0) == owner for b in range(len(ex.peer.nslices()))), \
             "wrong xGMI bucket kind for the plan"
-        sums = []
-        for i in range(STEPS):
-            tr.train_step(i)
-            sums.append(_canon(tr.params, tr.plan.tensor_offsets).double().sum().item())
-        torch.cuda.synchronize()
-        ex.check()
-        acc = tr.evaluate()
-        torch.save({"params": _canon(tr.params, tr.plan.tensor_offsets).cpu(), "acc": acc,
-                    "sums": sums,
-                    "t": {p: s.t for p, s in tr.servers.items()}},
-                   os.path.join(outdir, f"rank{rank}.pt"))
-        dist.barrier()
-        dist.destroy_process_group()
-    except Exception:
-        traceback.print_exc()
-        raise
+        rec = oc.sync_rank_record(
+            tr, STEPS, lambda tr, i: {"sums": _checksum(tr.params, tr.plan.tensor_offsets)})
+        rec["acc"] = tr.evaluate()
+        torch.save(rec, os.path.join(outdir, f"rank{rank}.pt"))
 
 
 def _simulate(world, kw):
     from ddl_amd.models import engine_segments
-    from ddl_amd.models.hip_engine import HipEngine
-    from ddl_amd.models.mnist_cnn import init_params_
-    from ddl_amd.ops import native, rng
-    from ddl_amd.ops.adam import AdamHyper, adam_coeffs
     from ddl_amd.parallel.sharding import make_plan
-    from ddl_amd.utils.data import synthetic_mnist, batch_indices
-    dev = torch.device("cuda", 0)
-    data = synthetic_mnist(2000, 500, seed=5).to(dev)
-    plan = make_plan("flat", world, buckets=engine_segments("hip", dev))
-    params = torch.zeros(plan.total, device=dev)
-    init_params_(params, plan.tensor_offsets, 0)
-    grads = torch.zeros_like(params)
-    acc, m, v = torch.zeros_like(params), torch.zeros_like(params), torch.zeros_like(params)
-    eng = HipEngine(params, grads, plan.tensor_offsets, batch=100, graph=False)
-    h = AdamHyper()
-    coef = kw.get("coef", [1.0] * world)
+    plan = make_plan("flat", world, buckets=engine_segments("hip", torch.device("cuda", 0)))
     sums = []
-    for step in range(STEPS):
-        acc.zero_()
-        for r in range(world):
-            lo, hi = batch_indices(step, 100, data.total_batch, r, world, "stride")
-            eng.forward_backward(data.x_train[lo:hi], data.y_train[lo:hi], 0.5,
-                                 rng.step_seed(0, r, step))
-            acc.add_(grads * coef[r] if coef[r] != 1.0 else grads)
-        scale = 1.0 / world if kw.get("grad_reduce") == "mean" else 1.0
-        native.ops().adam_flat(params, acc, m, v, adam_coeffs(h, step + 1), h.beta1, h.beta2,
-                               h.eps, scale)
-        sums.append(_canon(params, plan.tensor_offsets).double().sum().item())
-    torch.cuda.synchronize()
-    return _canon(params, plan.tensor_offsets).cpu(), sums
+    ref = oc.simulate_sync(
+        world, STEPS, 100, oc.dataset_on_card(2000, 500), plan, coef=kw.get("coef"),
+        scale=1.0 / world if kw.get("grad_reduce") == "mean" else 1.0,
+        after_step=lambda step, params, *_: sums.append(_checksum(params, plan.tensor_offsets)))
+    return ref, sums
 
 
 @pytest.mark.parametrize("world,kw", [
@@ -168,12 +94,8 @@ def _simulate(world, kw):
     pytest.param(8, dict(shard="greedy", _env=W8_ENV), id="w8-greedy"),
 ])
 def test_xgmi_exchange_matches_simulation(tmp_path, world, kw):
-    import torch.multiprocessing as mp
-    if world == 8:
-        _inproc_rank0(_rank, world, free_port(), str(tmp_path), kw)
-    else:
-        mp.spawn(_rank, args=(world, free_port(), str(tmp_path), kw), nprocs=world, join=True)
-    recs = [torch.load(os.path.join(tmp_path, f"rank{r}.pt")) for r in range(world)]
+    _job(_rank, world, free_port(), str(tmp_path), kw)
+    recs = oc.load_ranks(tmp_path, world)
     for rec in recs[1:]:
         assert torch.equal(rec["params"], recs[0]["params"])
         assert rec["acc"] == recs[0]["acc"]
@@ -190,24 +112,9 @@ def test_xgmi_exchange_matches_simulation(tmp_path, world, kw):
 def _handoff_rank(rank, world, port, outdir, perturb):
     """One-card W = 2 xGMI sync trainer; its READY-flag hand-off check with (perturb) or without
     an injected digest disagreement on the last rank."""
-    if ROOT not in sys.path:
-        sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
-                      WORLD_SIZE=str(world), LOCAL_RANK=str(rank), DDL_DIST_BACKEND="gloo",
-                      DDL_XGMI_TIMEOUT_S="20")
-    try:
-        import torch.distributed as dist
-        from ddl_amd.config import TrainConfig
-        from ddl_amd.parallel.comm import init_distributed
+    with oc.rank_session(rank, world, port) as me:
         from ddl_amd.parallel.native_exchange import NativeUnavailable
-        from ddl_amd.parallel.roles import Trainer
-        from ddl_amd.utils.data import synthetic_mnist
-        env = init_distributed()
-        cfg = TrainConfig(mode="sync", shard="flat", steps=STEPS, batch_size=100, eval_every=0,
-                          engine="hip", quiet=True, data_sharding="stride",
-                          exchange_backend="xgmi")
-        tr = Trainer(cfg, env, dataset=synthetic_mnist(2000, 500, seed=5))
-        assert tr.exchange.peer is not None, "xgmi path not taken"
+        tr = oc.xgmi_trainer(me.env, "sync", STEPS, 100, _data(), shard="flat")
         try:
             out = tr.exchange.handoff_check(tr, steps=2,
                                             _perturb_rank=world - 1 if perturb else None)
@@ -215,13 +122,7 @@ def _handoff_rank(rank, world, port, outdir, perturb):
             out = {"refused": str(e)}
         torch.cuda.synchronize()
         torch.save(out, os.path.join(outdir, f"rank{rank}.pt"))
-        dist.barrier()
-        tr.exchange.close()
-        dist.barrier()
-        dist.destroy_process_group()
-    except Exception:
-        traceback.print_exc()
-        raise
+        me.close_single(tr.exchange)
 
 
 @pytest.mark.parametrize("perturb", [False, True])
@@ -229,12 +130,9 @@ def test_handoff_check_refuses_diverged_replicas(tmp_path, perturb):
     """One card, W = 2 over xGMI: the hand-off check proves the READY flags (both ranks, same
     bits); with a digest disagreement injected on rank 1 both ranks refuse the data plane
     (NativeUnavailable) instead of falling back to events."""
-    import torch.multiprocessing as mp
     world = 2
-    mp.spawn(_handoff_rank, args=(world, free_port(), str(tmp_path), perturb), nprocs=world,
-             join=True)
-    outs = [torch.load(os.path.join(tmp_path, f"rank{r}.pt"), weights_only=False)
-            for r in range(world)]
+    oc.run_ranks(_handoff_rank, world, free_port(), str(tmp_path), perturb, limit_s=oc.LIMIT_S)
+    outs = oc.load_ranks(tmp_path, world)
     if perturb:
         assert all("refused" in o and "diverge" in o["refused"] for o in outs), outs
     else:
@@ -245,29 +143,11 @@ ASYNC_STEPS = 6
 
 
 def _async_rank(rank, world, port, outdir, kw):
-    if ROOT not in sys.path:
-        sys.path.insert(0, ROOT)
     kw = dict(kw)
     extra_env = kw.pop("_env", {})
     kw.pop("_ps", None)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
-                      WORLD_SIZE=str(world), LOCAL_RANK=str(rank), DDL_DIST_BACKEND="gloo",
-                      DDL_XGMI_TIMEOUT_S="20")
-    os.environ.update(extra_env)
-    try:
-        import torch.distributed as dist
-        from ddl_amd.config import TrainConfig
-        from ddl_amd.parallel.async_xgmi import AsyncPeerExchange
-        from ddl_amd.parallel.comm import init_distributed
-        from ddl_amd.parallel.roles import Trainer
-        from ddl_amd.utils.data import synthetic_mnist
-        env = init_distributed()
-        cfg = TrainConfig(mode="async", steps=ASYNC_STEPS, batch_size=100, eval_every=0,
-                          engine="hip", quiet=True, data_sharding="stride",
-                          exchange_backend="xgmi", check_provenance=True, watchdog_s=120.0,
-                          **kw)
-        tr = Trainer(cfg, env, dataset=synthetic_mnist(2000, 500, seed=5))
-        assert isinstance(tr.exchange, AsyncPeerExchange), type(tr.exchange)
+    with oc.rank_session(rank, world, port, env=extra_env) as me:
+        tr = oc.xgmi_trainer(me.env, "async", ASYNC_STEPS, 100, _data(), **kw)
         want_native = extra_env.get("DDL_ASYNC_NATIVE", "1") == "1"
         assert (tr.exchange.runner is not None) == want_native, "native async step not taken"
         s = tr.train()  # verify_provenance runs inside (check_provenance=True)
@@ -283,12 +163,6 @@ def _async_rank(rank, world, port, outdir, kw):
                     "ranges": {p: tr.plan.ps_segments(p)[0] for p in tr.servers},
                     "acc": s["final_acc"]},
                    os.path.join(outdir, f"rank{rank}.pt"))
-        if world > 1:
-            dist.barrier()
-            dist.destroy_process_group()
-    except Exception:
-        traceback.print_exc()
-        raise
 
 
 @pytest.mark.parametrize("world,kw", [
@@ -309,13 +183,8 @@ def _async_rank(rank, world, port, outdir, kw):
                                                    DDL_XGMI_TIMEOUT_S="60")), id="w8-greedy"),
 ])
 def test_async_xgmi_serves_every_push(tmp_path, world, kw):
-    import torch.multiprocessing as mp
-    if world == 8:
-        _inproc_rank0(_async_rank, world, free_port(), str(tmp_path), kw)
-    else:
-        mp.spawn(_async_rank, args=(world, free_port(), str(tmp_path), kw), nprocs=world,
-                 join=True)
-    recs = [torch.load(os.path.join(tmp_path, f"rank{r}.pt")) for r in range(world)]
+    _job(_async_rank, world, free_port(), str(tmp_path), kw)
+    recs = oc.load_ranks(tmp_path, world)
     n_ps = sum(len(rec["ps"]) for rec in recs)
     assert n_ps == kw.get("_ps", kw.get("num_ps", 1 if kw["shard"] == "none" else world))
     for rec in recs:
@@ -337,14 +206,13 @@ def test_async_inline_apply_equals_service_w1(tmp_path, shard, ps):
     blocks of the next backward launch) instead of through the board, the service's apply kernel
     and the gate.  Same Adam arithmetic, same per-PS step counters, same order: the worker's
     parameters and every PS's state must be bit-identical to the service path's."""
-    import torch.multiprocessing as mp
     recs = {}
     for mode in ("1", "0"):
         d = tmp_path / f"inline{mode}"
         d.mkdir()
         kw = dict(shard=shard, _ps=ps, _env=dict(DDL_ASYNC_INLINE=mode))
-        mp.spawn(_async_rank, args=(1, free_port(), str(d), kw), nprocs=1, join=True)
-        recs[mode] = torch.load(d / "rank0.pt")
+        oc.run_ranks(_async_rank, 1, free_port(), str(d), kw, limit_s=oc.LIMIT_S)
+        recs[mode] = oc.load_ranks(d, 1)[0]
     a, b = recs["1"], recs["0"]
     assert len(a["ps"]) == ps
     assert a["served"] == b["served"] == ps * ASYNC_STEPS
@@ -357,31 +225,16 @@ def test_async_inline_apply_equals_service_w1(tmp_path, shard, ps):
 
 
 def _ckpt_rank(rank, world, port, outdir, kw):
-    if ROOT not in sys.path:
-        sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
-                      WORLD_SIZE=str(world), LOCAL_RANK=str(rank), DDL_DIST_BACKEND="gloo",
-                      DDL_XGMI_TIMEOUT_S="20")
-    try:
-        import torch.distributed as dist
+    with oc.rank_session(rank, world, port) as me:
         from ddl_amd.config import TrainConfig
-        from ddl_amd.parallel.comm import init_distributed
         from ddl_amd.parallel.roles import Trainer
-        from ddl_amd.utils.data import synthetic_mnist
-        env = init_distributed()
         cfg = TrainConfig(mode="async", steps=6, batch_size=100, eval_every=0, engine="hip",
                           quiet=True, data_sharding="stride", exchange_backend="xgmi",
                           checkpoint_dir=os.path.join(outdir, "ck"), watchdog_s=120.0, **kw)
-        tr = Trainer(cfg, env, dataset=synthetic_mnist(2000, 500, seed=5))
+        tr = Trainer(cfg, me.env, dataset=_data())
         tr.train()  # checkpoint_every=3: a mid-run snapshot while the PS services run
         torch.save({"t": {p: s.t for p, s in tr.servers.items()}},
                    os.path.join(outdir, f"final{rank}.pt"))
-        if world > 1:
-            dist.barrier()
-            dist.destroy_process_group()
-    except Exception:
-        traceback.print_exc()
-        raise
 
 
 @pytest.mark.parametrize("world", [2, 1])  # W = 1: the in-line applies
@@ -390,12 +243,11 @@ def test_async_xgmi_midrun_checkpoint_is_consistent(tmp_path, world):
     advanced (beta powers consistent with the manifest's t) and a snapshot taken with the
     service paused; the final one equals the services' end state."""
     import json
-    import torch.multiprocessing as mp
     from safetensors.torch import load_file
     # the step-3 save runs while the peer's pushes are being served (it must neither deadlock
     # against the peer nor tear the PS state); the end-of-run save overwrites it and is checked
-    mp.spawn(_ckpt_rank, args=(world, free_port(), str(tmp_path), dict(checkpoint_every=3)),
-             nprocs=world, join=True)
+    oc.run_ranks(_ckpt_rank, world, free_port(), str(tmp_path), dict(checkpoint_every=3),
+                 limit_s=oc.LIMIT_S)
     man = json.load(open(tmp_path / "ck" / "manifest.json"))
     final = {}
     for r in range(world):
@@ -425,30 +277,16 @@ def test_xgmi_job_survivor_exits_when_a_peer_fails(tmp_path, fault):
 
 
 def _eval_rank(rank, world, port, outdir):
-    if ROOT not in sys.path:
-        sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
-                      WORLD_SIZE=str(world), LOCAL_RANK=str(rank), DDL_DIST_BACKEND="gloo",
-                      DDL_XGMI_TIMEOUT_S="20")
-    try:
-        import torch.distributed as dist
+    with oc.rank_session(rank, world, port) as me:
         from ddl_amd.config import TrainConfig
-        from ddl_amd.parallel.comm import init_distributed
         from ddl_amd.parallel.roles import Trainer
-        from ddl_amd.utils.data import synthetic_mnist
-        env = init_distributed()
         cfg = TrainConfig(mode="sync", shard="flat", steps=30, batch_size=100, eval_every=10,
                           engine="hip", quiet=True, data_sharding="stride",
                           exchange_backend="xgmi", eval_async=True, watchdog_s=120.0)
-        tr = Trainer(cfg, env, dataset=synthetic_mnist(3000, 500, seed=5))
+        tr = Trainer(cfg, me.env, dataset=_data(3000))
         s = tr.train()
         torch.save({"acc": s["final_acc"], "evals": len(tr.history)},
                    os.path.join(outdir, f"eval{rank}.pt"))
-        dist.barrier()
-        dist.destroy_process_group()
-    except Exception:
-        traceback.print_exc()
-        raise
 
 
 def test_xgmi_sync_with_side_stream_eval_completes(tmp_path):
@@ -457,8 +295,7 @@ def test_xgmi_sync_with_side_stream_eval_completes(tmp_path):
     or the comm stream's READY gate can share its hardware queue and wait behind the very launch
     that releases it (this job stalled before the AsyncEvaluator's training stream went to
     normal priority)."""
-    import torch.multiprocessing as mp
-    mp.spawn(_eval_rank, args=(2, free_port(), str(tmp_path)), nprocs=2, join=True)
+    oc.run_ranks(_eval_rank, 2, free_port(), str(tmp_path), limit_s=oc.LIMIT_S)
     for r in range(2):
         rec = torch.load(os.path.join(tmp_path, f"eval{r}.pt"))
         assert rec["evals"] >= 3 and rec["acc"] > 0.1
