@@ -31,6 +31,8 @@ class TrainConfig:
     nesterov: bool = False          # momentum only: step along mu * m' + g
     clip_norm: float = 0.0          # clip each worker's gradient to this global norm; 0 = off
     accum_steps: int = 1            # micro-batches of batch_size per step (one update); 1 = off
+    shuffle: bool = False           # a fresh order of the training set every pass (ops/shuffle.py)
+    augment_shift: int = 0          # translate each training image by up to this many pixels; 0 = off
     keep_prob: float = 0.5
     eval_every: int = 10            # 0 disables periodic eval
     data: str = "synthetic"
@@ -63,6 +65,7 @@ class TrainConfig:
         check_optimizer_options(self.optimizer, self.momentum, self.weight_decay, self.nesterov)
         check_clip_norm(self.clip_norm)
         check_accum_steps(self.accum_steps)
+        check_augment_shift(self.augment_shift)
 
     def to_dict(self):
         return asdict(self)
@@ -89,6 +92,12 @@ def check_accum_steps(accum_steps: int) -> None:
     """Refuse a micro-batch count below 1 (or not an integer); 1 switches accumulation off."""
     from .ops.accum import check_accum_steps as check
     check(accum_steps)
+
+
+def check_augment_shift(augment_shift: int) -> None:
+    """Refuse a shift that is no integer in 0..8; 0 switches the augmentation off."""
+    from .ops.shuffle import check_augment_shift as check
+    check(augment_shift)
 
 
 def add_args(p: argparse.ArgumentParser, mode_default: str = "sync") -> argparse.ArgumentParser:
@@ -125,6 +134,14 @@ def add_args(p: argparse.ArgumentParser, mode_default: str = "sync") -> argparse
                         "per K backward passes); steps, --eval-every, --checkpoint-every and "
                         "--max-steps stay in updates; K > 1 runs without backward/exchange "
                         "overlap; 1 = off")
+    p.add_argument("--shuffle", action="store_true",
+                   help="read every pass over the training set in a fresh pseudo-random order, "
+                        "without replacement: a function of --seed, the epoch and the position, "
+                        "the same on every rank and after --resume, evaluated on the device")
+    p.add_argument("--augment-shift", type=int, default=d.augment_shift,
+                   help="translate every training image by a per-draw (dx, dy), each uniform in "
+                        "[-S, S] pixels, zero-filled (training stream only, never eval); "
+                        "0..8, 0 = off")
     p.add_argument("--keep-prob", type=float, default=d.keep_prob)
     p.add_argument("--eval-every", type=int, default=d.eval_every)
     p.add_argument("--data", default=d.data)
@@ -171,7 +188,8 @@ def from_args(a: argparse.Namespace) -> TrainConfig:
         mode=mode, shard=shard, num_ps=a.num_ps, epochs=a.epochs, batch_size=a.batch_size,
         steps=a.steps, lr=a.lr, optimizer=a.optimizer, momentum=a.momentum,
         weight_decay=a.weight_decay, nesterov=a.nesterov, clip_norm=a.clip_norm,
-        accum_steps=a.accum_steps, keep_prob=a.keep_prob,
+        accum_steps=a.accum_steps, shuffle=a.shuffle, augment_shift=a.augment_shift,
+        keep_prob=a.keep_prob,
         eval_every=a.eval_every, data=a.data, data_sharding=a.data_sharding,
         grad_reduce=a.grad_reduce, ref_quirks=a.ref_quirks, seed=a.seed, engine=a.engine,
         graph=a.graph and not a.no_graph, native_exchange=not a.no_native_exchange,

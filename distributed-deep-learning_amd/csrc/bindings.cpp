@@ -165,6 +165,46 @@ void accum_grads(at::Tensor grads, at::Tensor acc, std::vector<std::pair<int64_t
                     cur_stream(), (int)max_grid);
 }
 
+// One training batch (kernels/batch.hip): rows [0, b) of xb and yb from the resident training set,
+// shuffled and / or shifted (no host sync, no allocation); rows from b on keep their contents
+void assemble_batch(at::Tensor x_train, at::Tensor y_train, at::Tensor xb, at::Tensor yb,
+                    int64_t b, int64_t base, int64_t key, int64_t key_shift, int64_t s,
+                    bool shuffle) {
+  check_f32_cuda(x_train, "x_train");
+  check_f32_cuda(xb, "xb");
+  auto check_labels = [](const at::Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kLong && t.is_contiguous() && t.dim() == 1,
+                name, " must be a contiguous int64 GPU vector");
+  };
+  check_labels(y_train, "y_train");
+  check_labels(yb, "yb");
+  TORCH_CHECK(x_train.dim() == 2 && x_train.size(1) == 784 && xb.dim() == 2 && xb.size(1) == 784,
+              "assemble_batch: x_train and xb must be [rows, 784]");
+  const int64_t n = x_train.size(0);
+  TORCH_CHECK(y_train.size(0) == n, "assemble_batch: y_train must have a label per training row");
+  TORCH_CHECK(n >= 1 && n <= INT32_MAX, "assemble_batch: training rows in 1..2^31 - 1");
+  TORCH_CHECK(b >= 1 && b <= xb.size(0) && b <= yb.size(0),
+              "assemble_batch: xb and yb must hold the batch");
+  TORCH_CHECK(base >= 0 && base + b <= n, "assemble_batch: the batch lies outside the training rows");
+  TORCH_CHECK(s >= 0 && s <= 8, "assemble_batch: shift in 0..8");
+  TORCH_CHECK(key >= 0 && key <= 0xFFFFFFFFLL && key_shift >= 0 && key_shift <= 0xFFFFFFFFLL,
+              "assemble_batch: keys are 32-bit");
+  TORCH_CHECK(x_train.device() == xb.device() && y_train.device() == xb.device() &&
+              yb.device() == xb.device(), "assemble_batch: tensors on different devices");
+  // apart: the training set is read while the batch is written
+  const char* t0 = reinterpret_cast<const char*>(x_train.data_ptr<float>());
+  const char* d0 = reinterpret_cast<const char*>(xb.data_ptr<float>());
+  TORCH_CHECK(d0 + 4 * xb.numel() <= t0 || t0 + 4 * x_train.numel() <= d0,
+              "assemble_batch: xb overlaps x_train");
+  const char* l0 = reinterpret_cast<const char*>(y_train.data_ptr<int64_t>());
+  const char* m0 = reinterpret_cast<const char*>(yb.data_ptr<int64_t>());
+  TORCH_CHECK(m0 + 8 * yb.numel() <= l0 || l0 + 8 * n <= m0, "assemble_batch: yb overlaps y_train");
+  c10::hip::HIPGuard guard(xb.device().index());
+  ddl::launch_assemble_batch(x_train.data_ptr<float>(), y_train.data_ptr<int64_t>(), n,
+                             xb.data_ptr<float>(), yb.data_ptr<int64_t>(), (int)b, base,
+                             (uint32_t)key, (uint32_t)key_shift, (int)s, shuffle, cur_stream());
+}
+
 // Python-facing wrapper of ddl::Engine: owns the workspace tensor.
 class PyEngine {
  public:
@@ -950,6 +990,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "2 grads := (acc + grads) * float32(1 / k)",
         py::arg("grads"), py::arg("acc"), py::arg("ranges"), py::arg("mode"), py::arg("k"),
         py::arg("max_grid") = 0);
+  m.def("assemble_batch", &assemble_batch,
+        "Rows [0, b) of xb [>= b,784] and yb [>= b] from the training set: row i is training row "
+        "perm(base + i; N, key) (base + i unshuffled), translated by its draw in [-s, s]^2",
+        py::arg("x_train"), py::arg("y_train"), py::arg("xb"), py::arg("yb"), py::arg("b"),
+        py::arg("base"), py::arg("key"), py::arg("key_shift"), py::arg("s"), py::arg("shuffle"));
   m.attr("CLIP_CHUNK") = (int)ddl::kClipChunk;
   m.attr("CLIP_SLOTS") = (int)ddl::kClipSlots;
   m.def("upd_decay", [](double lr, double weight_decay) {

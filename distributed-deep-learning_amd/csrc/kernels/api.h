@@ -104,6 +104,15 @@ struct GradStage {
   }
 };
 
+// ---- shuffled, shift-augmented batches (batch.hip) ------------------------------------------
+// rows [0, B) of xb [>= B,784] and yb [>= B] from the n training rows: row i is training row
+// perm(base + i; n, key) (base + i unshuffled) translated by the draw of (base + i, key_shift) in
+// [-s, s]^2, zero-filled (batch.h; ops/shuffle.py is the CPU twin).  base + B <= n; x_train and
+// xb 16-byte aligned and apart.  One launch, no host sync.
+void launch_assemble_batch(const float* x_train, const int64_t* y_train, int64_t n, float* xb,
+                           int64_t* yb, int B, int64_t base, uint32_t key, uint32_t key_shift,
+                           int s, bool shuffle, hipStream_t st);
+
 // ---- conv1 forward as a direct LDS-staged kernel (conv1.hip) --------------------------------
 // x [B,784], w [25,32], bias [32] -> pooled p1 [B,18,18,32] (halo layout) + codes [B,14,14,32]
 void launch_conv1_fwd(const float* x, const float* w, const float* bias, float* out,

@@ -28,6 +28,7 @@ from ..models.mnist_cnn import init_params_
 from ..ops import rng
 from ..ops import clip as clip_ops
 from ..ops import accum as accum_ops
+from ..ops import shuffle as shuffle_ops
 from ..ops.adam import AdamHyper
 from ..utils import metrics
 from ..utils.data import Dataset, get_dataset, batch_indices
@@ -133,6 +134,15 @@ class Trainer:
         # a step is one update: it consumes accum_steps micro-batches of batch_size images
         K = cfg.accum_steps
         self.steps = cfg.steps or (self.data.total_batch // (cfg.batch_size * K))
+        # --shuffle / --augment-shift: the one buffer pair Trainer.batch assembles every
+        # micro-batch into (ops/shuffle.py, csrc/kernels/batch.hip); with both off a batch stays
+        # a view of the resident set and nothing is allocated
+        self.batch_x: Optional[torch.Tensor] = None
+        self.batch_y: Optional[torch.Tensor] = None
+        if cfg.shuffle or cfg.augment_shift:
+            x, y = self.data.x_train, self.data.y_train
+            self.batch_x = torch.zeros(cfg.batch_size, x.shape[1], dtype=x.dtype, device=dev)
+            self.batch_y = torch.zeros(cfg.batch_size, dtype=y.dtype, device=dev)
         # Clipping by the global norm (ops/clip.py, csrc/kernels/clip.hip): the worker's own
         # gradient, before anything else reads it.  The norm needs the whole backward, so a
         # clipped step hands nothing over per segment: every exchange unit is the last segment's.
@@ -204,10 +214,32 @@ class Trainer:
                              check_provenance=cfg.check_provenance, job_id=job)
 
     # ---- one worker step (reference SyncWorker.work + pull + assign) -----------------------------
-    def batch(self, step: int):
-        lo, hi = batch_indices(step, self.cfg.batch_size, self.data.total_batch, self.env.rank,
-                               self.env.world, self.cfg.data_sharding)
-        return self.data.x_train[lo:hi], self.data.y_train[lo:hi]
+    def batch(self, step: int, epoch: Optional[int] = None):
+        """Micro-batch ``step`` of epoch ``epoch`` (default: the epoch ``global_step`` is in).
+        With --shuffle and --augment-shift off, views of the resident training set.  With either
+        on, the trainer's own batch buffers, assembled on the current stream (ops/shuffle.py,
+        csrc/kernels/batch.hip) from the raw batch number and the epoch alone.  One buffer pair:
+        every reader of a batch (conv1's weight gradient is the last) is ordered on the step's
+        stream ahead of the next assembly (docs/DESIGN.md, Shuffle)."""
+        cfg = self.cfg
+        if not (cfg.shuffle or cfg.augment_shift):
+            lo, hi = batch_indices(step, cfg.batch_size, self.data.total_batch, self.env.rank,
+                                   self.env.world, cfg.data_sharding)
+            return self.data.x_train[lo:hi], self.data.y_train[lo:hi]
+        if epoch is None:
+            epoch = self.global_step // self.steps
+        B = cfg.batch_size
+        base, key, key_shift = shuffle_ops.batch_rule(
+            cfg.seed, epoch, step, B, self.data.total_batch, self.env.rank, self.env.world,
+            cfg.data_sharding)
+        args = (self.data.x_train, self.data.y_train, self.batch_x, self.batch_y, B, base, key,
+                key_shift, cfg.augment_shift, cfg.shuffle)
+        if self.batch_x.is_cuda:
+            from ..ops import native
+            native.ops().assemble_batch(*args)
+        else:
+            shuffle_ops.assemble_batch(*args)
+        return self.batch_x, self.batch_y
 
     def clip_grads(self) -> None:
         """Clip this worker's gradient buffer in place (the Python-driven step paths); the

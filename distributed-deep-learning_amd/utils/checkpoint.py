@@ -8,7 +8,8 @@ slots ``/Adam`` (m), ``/Adam_1`` (v) and per-PS ``beta1_power``/``beta2_power``
 
 Layout of a checkpoint directory (safetensors, no pickle):
 
-  manifest.json                 plan, world, step, per-PS step counters, accum_steps
+  manifest.json                 plan, world, step, per-PS step counters, accum_steps,
+                                shuffle, augment_shift
   worker{r}.safetensors         mnist/v{i} for worker r (sync: only worker 0)
   ps{p}.safetensors             ParameterServer/v{i}[@a:b], .../Adam, .../Adam_1,
                                 ParameterServer/beta1_power, beta2_power
@@ -100,6 +101,10 @@ def save(trainer, path: str) -> None:
                    global_step=trainer.global_step, ps_t=ps_t,
                    # (saves happen on step boundaries only: the accumulator is never saved)
                    accum_steps=int(trainer.cfg.accum_steps),
+                   # (the order and the shifts are functions of the seed, the epoch and the
+                   # position: the two switches are all of their state)
+                   shuffle=bool(trainer.cfg.shuffle),
+                   augment_shift=int(trainer.cfg.augment_shift),
                    ps_segments=[[list(map(int, r)) for r in plan.ps_segments(p)]
                                 for p in range(plan.num_ps)])
         with open(os.path.join(path, "manifest.json"), "w") as f:
@@ -165,6 +170,15 @@ def load(trainer, path: str) -> None:
         raise ValueError(f"checkpoint {path} was written with --accum-steps {saved_k}; resuming "
                          f"with --accum-steps {trainer.cfg.accum_steps} would not continue that "
                          f"run (step {man['global_step']} reads other batches and dropout seeds)")
+    # likewise the input stream: shuffled or shifted, the same step reads other images (a manifest
+    # without the fields: both off)
+    saved_sh, saved_s = bool(man.get("shuffle", False)), int(man.get("augment_shift", 0))
+    now_sh, now_s = bool(trainer.cfg.shuffle), int(trainer.cfg.augment_shift)
+    if (saved_sh, saved_s) != (now_sh, now_s):
+        flags = lambda sh, s: f"{'--shuffle' if sh else 'no --shuffle'} --augment-shift {s}"  # noqa: E731
+        raise ValueError(f"checkpoint {path} was written with {flags(saved_sh, saved_s)}; "
+                         f"resuming with {flags(now_sh, now_s)} would not continue that run "
+                         f"(step {man['global_step']} reads other images)")
     wf = os.path.join(path, f"worker{env.rank}.safetensors")
     if not os.path.exists(wf):
         wf = os.path.join(path, "worker0.safetensors")

@@ -7,7 +7,9 @@ pandas, never shuffles, and every worker walks the *same* batches
 
 MI355X-first: the whole dataset (157 MB train + 31 MB test in fp32) is copied to HBM
 once and stays resident; a batch is a view, so there is no per-step host->device copy
-and no loader thread in the hot loop.
+and no loader thread in the hot loop.  With ``--shuffle`` or ``--augment-shift`` one kernel
+assembles the batch from the resident set instead (``ops/shuffle.py``), still without a copy
+from the host.
 
 There is no network in this environment, so unless a data file is supplied we use a
 *synthetic* MNIST-shaped set: 10 smooth random class prototypes, each sample a randomly
