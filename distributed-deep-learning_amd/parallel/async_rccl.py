@@ -16,13 +16,14 @@ async modes; the xGMI one (``async_xgmi.py``) needs no p2p kernels and is the de
 from __future__ import annotations
 
 import contextlib
-from typing import Dict, List, Tuple
+from typing import Dict
 
 import torch
 import torch.distributed as dist
 
 from ..ops import native
-from .comm import DistEnv
+from ..ops.adam import AdamHyper
+from .comm import AsyncBase, DistEnv
 from .ps import ParameterServer
 from .sharding import ShardPlan
 
@@ -31,33 +32,27 @@ class RcclAsyncUnavailable(RuntimeError):
     pass
 
 
-class RcclAsyncExchange:
+class RcclAsyncExchange(AsyncBase):
     backend = "rccl"
+    unavailable = RcclAsyncUnavailable
+    round_base = 1  # the service counts a worker's rounds at a PS from 1
 
     def __init__(self, plan: ShardPlan, env: DistEnv, params: torch.Tensor, grads: torch.Tensor,
                  servers: Dict[int, ParameterServer], steps_per_worker: int, job_id: str,
-                 optimizer: str = "adam", check_provenance: bool = False):
+                 optimizer: str = "adam", check_provenance: bool = False, engine=None,
+                 stage=None):
         if not params.is_cuda or not native.available():
             raise RcclAsyncUnavailable("needs the extension and a GPU")
         if env.world > 1 and env.backend != "nccl":
             raise RcclAsyncUnavailable("needs the nccl (RCCL) default group to exchange the id")
         if optimizer not in ("adam", "momentum", "sgd"):
             raise RcclAsyncUnavailable(f"no '{optimizer}' update")
-        P, W, r = plan.num_ps, env.world, env.rank
-        for p in range(P):
-            if len(plan.ps_segments(p)) != 1:
-                raise RcclAsyncUnavailable("async mode needs one contiguous range per PS")
-        self.plan, self.env, self.params, self.grads = plan, env, params, grads
-        self.servers = servers
-        self.steps = steps_per_worker
-        self.check_provenance = check_provenance
-        self.ranges: List[Tuple[int, int]] = [plan.ps_segments(p)[0] for p in range(P)]
-        self.hosts = [plan.host_rank(p, W) for p in range(P)]
-        h = next(iter(servers.values())).h if servers else None
-        mom = 0.0 if optimizer == "sgd" else (next(iter(servers.values())).momentum
-                                              if servers else 0.9)
-        hyper = h or _default_hyper()
-        ps0 = next(iter(servers.values())) if servers else None
+        super().__init__(plan, env, params, grads, servers, steps_per_worker, check_provenance,
+                         engine, stage)
+        W, r = env.world, env.rank
+        ps0 = next(iter(servers.values()), None)  # (a rank may host no PS)
+        hyper = ps0.h if ps0 is not None else AdamHyper()
+        mom = 0.0 if optimizer == "sgd" else (ps0.momentum if ps0 is not None else 0.9)
         wd, nesterov = (ps0.weight_decay, ps0.nesterov) if ps0 is not None else (0.0, False)
         ops = native.ops()
         ps_list = [(p, ps.params, ps.m, ps.v, ps.t) for p, ps in servers.items()]
@@ -83,12 +78,6 @@ class RcclAsyncExchange:
         if W > 1:
             dist.barrier()
         self.svc.open_boxes(False)
-        self.served = 0
-        self.provenance: List[Tuple[int, int, int, int]] = []
-
-    def _expected(self) -> int:
-        W, r = self.env.world, self.env.rank
-        return sum(1 for hh in self.hosts if hh == r) * (W - 1) * self.steps
 
     def start(self) -> None:
         # the PS step counters may have been restored (checkpoint load) after the native object
@@ -100,18 +89,12 @@ class RcclAsyncExchange:
     def push_pull(self) -> None:
         self.svc.push_pull()
 
-    def _sync_counters(self) -> None:
-        for p, ps in self.servers.items():
-            n = self.svc.t(p) - ps.t
-            ps.t += n
-            ps.updates += n
-
     @contextlib.contextmanager
     def paused(self):
         """Checkpoint hook: no session is served and no update issued inside the block."""
         self.svc.pause()
         try:
-            self._sync_counters()
+            self._sync_counters(self.svc.t)
             yield
         finally:
             self.svc.resume()
@@ -120,28 +103,4 @@ class RcclAsyncExchange:
         try:
             self.svc.join()
         finally:
-            self._sync_counters()
-            self.served = self.svc.served()
-            if self.check_provenance:
-                # (worker, ps, that worker's round at the PS from 1, PS step) -> rounds from 0
-                self.provenance = [(w, p, k - 1, t) for (w, p, k, t) in self.svc.provenance()]
-
-    def verify_provenance(self) -> None:
-        """Every hosted PS applied exactly `steps` pushes of every worker, in round order, and
-        its step counter advanced once per push."""
-        for p in self.servers:
-            for w in range(self.env.world):
-                steps = [s for (ww, pp, s, _) in self.provenance if ww == w and pp == p]
-                if steps != list(range(self.steps)):
-                    raise RuntimeError(f"provenance: PS {p} / worker {w} steps {steps[:5]}...")
-            ts = [t for (_, pp, _, t) in self.provenance if pp == p]
-            if ts != sorted(ts) or len(set(ts)) != len(ts):
-                raise RuntimeError(f"provenance: PS {p} step counter not strictly increasing")
-
-    def close(self) -> None:
-        pass
-
-
-def _default_hyper():
-    from ..ops.adam import AdamHyper
-    return AdamHyper()
+            self._collect(self.svc.t, self.svc.served(), self.svc.provenance)

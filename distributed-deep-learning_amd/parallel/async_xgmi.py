@@ -29,13 +29,14 @@ from __future__ import annotations
 
 import contextlib
 import os
-from typing import Dict, List, Optional, Tuple
+from typing import Dict
 
 import torch
 import torch.distributed as dist
 
 from ..ops import native
-from .comm import DistEnv, agree
+from ..utils.tracing import trace_range
+from .comm import AsyncBase, DistEnv, agree
 from .ps import ParameterServer
 from .sharding import ShardPlan
 
@@ -44,36 +45,26 @@ class AsyncPeerUnavailable(RuntimeError):
     pass
 
 
-class _RunnerCounters:
-    """The runner's in-line step counters behind the service's ``t(ps)``."""
-
-    def __init__(self, runner):
-        self.t = runner.inline_t
-
-
-class AsyncPeerExchange:
+class AsyncPeerExchange(AsyncBase):
     backend = "xgmi"
+    unavailable = AsyncPeerUnavailable
+    serves_self = True   # a worker's push to a PS on its own rank goes over the board too
+    round_base = 2       # round 1 is the set-up self-test
 
     def __init__(self, plan: ShardPlan, env: DistEnv, params: torch.Tensor, grads: torch.Tensor,
                  servers: Dict[int, ParameterServer], steps_per_worker: int,
                  grad_reduce: str = "sum", job_id: str = "ddl",
-                 check_provenance: bool = False, optimizer: str = "adam"):
+                 check_provenance: bool = False, optimizer: str = "adam", engine=None,
+                 stage=None):
         if not params.is_cuda or not native.available():
             raise AsyncPeerUnavailable("async xGMI exchange needs the extension and a GPU")
         if optimizer not in ("adam", "momentum", "sgd"):
             raise AsyncPeerUnavailable(f"async xGMI exchange has no '{optimizer}' update")
-        P, W, r = plan.num_ps, env.world, env.rank
-        for p in range(P):
-            if len(plan.ps_segments(p)) != 1:
-                raise AsyncPeerUnavailable("async mode needs one contiguous range per PS")
-        self.plan, self.env, self.params, self.grads = plan, env, params, grads
-        self.servers = servers
-        self.steps = steps_per_worker
-        self.grad_scale = 1.0  # the async PS applies each worker's gradient as-is
+        super().__init__(plan, env, params, grads, servers, steps_per_worker, check_provenance,
+                         engine, stage)
+        W, r = env.world, env.rank
         self.opt = 0 if optimizer == "adam" else 1  # sgd: the momentum update with mu = 0
         self.mu = 0.0 if optimizer == "sgd" else None
-        self.ranges: List[Tuple[int, int]] = [plan.ps_segments(p)[0] for p in range(P)]
-        self.hosts = [plan.host_rank(p, W) for p in range(P)]
         ops = native.ops()
 
         peer, mine, why = None, None, ""
@@ -118,23 +109,19 @@ class AsyncPeerExchange:
         self.coef = 1.0
         self.timeout_s = 600.0
         self._svc = None
-        self.served = 0
-        self.check_provenance = check_provenance
-        self.provenance: List[Tuple[int, int, int, int]] = []
-        self.runner = None
-        self.service_mode = None
         self.inline = False
         self.inline_ok = False
 
     # -- the native worker step ----------------------------------------------------------------------
-    def attach_runner(self, engine, segments, accum=None) -> None:
+    def attach_runner(self, segments) -> None:
         """Issue the worker step from C++ (csrc/kernels/async_runner.hip) — forward, the backward
         segments with each PS's push launched as soon as its range is complete (the push posts
         itself on the arrival board), the previous round's pull as a host wait at the start of
         the step — when the engine is the HIP one.  DDL_ASYNC_NATIVE=0 keeps the Python
-        push_pull path.  accum: the trainer's (K, ranges, accumulator) under --accum-steps: the
-        runner then takes K - 1 native_accumulate() calls ahead of every native_step()."""
+        push_pull path.  The runner takes the stage's clip and accumulation triples: under
+        --accum-steps, K - 1 accumulate() calls ahead of every step()."""
         from ..models.layout import TENSORS
+        engine = self.engine
         if getattr(engine, "name", "") != "hip" or os.environ.get("DDL_ASYNC_NATIVE", "1") != "1":
             return
         seg_of = {t: s for s, ts in enumerate(segments) for t in ts}
@@ -145,8 +132,7 @@ class AsyncPeerExchange:
             seg_of_ps.append(max(seg_of[t] for t in ts))
         self.runner = native.ops().AsyncRunner(engine.eng, self.peer, self.env.world,
                                                self.env.rank, seg_of_ps, self.epoch)
-        if accum is not None:
-            self.runner.set_accum(*accum)
+        self.stage.attach(self.runner)
         # one worker hosting every PS (W = 1) with Adam: the pushes are applied in-line, as
         # tail blocks of the next backward launch (async_runner.hip set_inline); start() turns
         # it on once the PS state is final (a resume loads it after this point).
@@ -154,18 +140,16 @@ class AsyncPeerExchange:
         self.inline_ok = (self.env.world == 1 and self.opt == 0
                           and os.environ.get("DDL_ASYNC_INLINE", "1") == "1")
 
-    def native_step(self, engine, x, y, keep_prob: float, seed: int) -> None:
-        engine._set_keep(keep_prob)
-        self.runner.step(x if x.is_contiguous() else x.contiguous(), y, seed & 0xFFFFFFFF,
-                         self.timeout_s)
-        self.epoch += 1
-
-    def native_accumulate(self, engine, x, y, keep_prob: float, seed: int) -> None:
-        """A non-final micro-batch of an accumulated round: no round is opened, nothing is
-        pushed (the round counter stays)."""
-        engine._set_keep(keep_prob)
-        self.runner.accumulate(x if x.is_contiguous() else x.contiguous(), y, seed & 0xFFFFFFFF,
-                               self.timeout_s)
+    def _micro(self, x, y, keep_prob: float, seed: int, final: bool) -> None:
+        """With the runner, step() and accumulate() are its own.  A non-final micro-batch of an
+        accumulated round opens no round and pushes nothing (the round counter stays)."""
+        if self.runner is None:
+            return super()._micro(x, y, keep_prob, seed, final)
+        with trace_range("step_native_async"):
+            run = self.runner.step if final else self.runner.accumulate
+            run(*self._native_args(x, y, keep_prob, seed), self.timeout_s)
+        if final:
+            self.epoch += 1
 
     def drain_round(self) -> None:
         """The round in flight (native step) has come back: this worker's parameters are final
@@ -215,10 +199,6 @@ class AsyncPeerExchange:
         self.epoch = 1                                   # worker rounds done
 
     # -- PS service thread -------------------------------------------------------------------------
-    def _expected(self) -> int:
-        W, r = self.env.world, self.env.rank
-        return sum(1 for h in self.hosts if h == r) * W * self.steps
-
     def start(self) -> None:
         """The service loop in C++ (xgmi_async.hip AsyncService): no Python and no GIL between
         a remote worker's push and its apply kernel."""
@@ -246,26 +226,15 @@ class AsyncPeerExchange:
         self._svc.start(n)
         self.service_mode = self._svc.mode()  # "host": the native board-scan service
 
-    def _sync_counters(self, svc) -> None:
-        """The native service advances each hosted PS's step counter; mirror it into the
-        Python ParameterServer objects (checkpoints and reports read those)."""
-        for p, ps in self.servers.items():
-            n = svc.t(p) - ps.t
-            ps.t += n
-            ps.updates += n
-
-    def _sync_inline(self) -> None:
-        """In-line applies: the runner holds the step counters and the worker buffer holds the
-        parameters (drain_round wrote them back into the PS objects' private copies)."""
-        self._sync_counters(_RunnerCounters(self.runner))
-
     @contextlib.contextmanager
     def paused(self):
         """Checkpoint hook: no PS update is issued inside the block and every issued one has
         completed, so each hosted PS's parameters, m, v and t are one consistent step."""
         if self.inline:  # every apply is on this worker's stream: drained by drain_round
+            # (the runner holds the step counters; drain_round wrote the parameters back into
+            # the PS objects' private copies)
             self.drain_round()
-            self._sync_inline()
+            self._sync_counters(self.runner.inline_t)
             yield
             return
         svc = self._svc
@@ -274,7 +243,7 @@ class AsyncPeerExchange:
             return
         svc.pause()
         try:
-            self._sync_counters(svc)
+            self._sync_counters(svc.t)
             yield
         finally:
             svc.resume()
@@ -282,34 +251,18 @@ class AsyncPeerExchange:
     def join(self) -> None:
         self.drain_round()  # this worker's last round (the reference's final pull)
         if self.inline:
-            self._sync_inline()
-            self.served = sum(self.runner.inline_t(p) - t0 for p, t0 in self._inline_t0.items())
-            if self.check_provenance:
-                self.provenance = [(w, p, e - 2, t)
-                                   for (w, p, e, t) in self.runner.inline_provenance()]
+            run = self.runner
+            self._collect(run.inline_t, sum(run.inline_t(p) - t0
+                                            for p, t0 in self._inline_t0.items()),
+                          run.inline_provenance)
         if self._svc is not None:
             svc, self._svc = self._svc, None
             try:
                 svc.join()
             finally:
-                self._sync_counters(svc)
-                self.served = svc.served()
-                if self.check_provenance:
-                    self.provenance = [(w, p, e - 2, t) for (w, p, e, t) in svc.provenance()]
+                self._collect(svc.t, svc.served(), svc.provenance)
         if self.peer.error():
             raise RuntimeError(f"async xGMI wait timed out (code {self.peer.error()})")
-
-    def verify_provenance(self) -> None:
-        """Every hosted PS applied exactly `steps` pushes of every worker, in step order, and
-        its step counter advanced once per push."""
-        for p in self.servers:
-            for w in range(self.env.world):
-                steps = [s for (ww, pp, s, _) in self.provenance if ww == w and pp == p]
-                if steps != list(range(self.steps)):
-                    raise RuntimeError(f"provenance: PS {p} / worker {w} steps {steps[:5]}...")
-            ts = [t for (_, pp, _, t) in self.provenance if pp == p]
-            if ts != sorted(ts) or len(set(ts)) != len(ts):
-                raise RuntimeError(f"provenance: PS {p} step counter not strictly increasing")
 
     # -- worker side --------------------------------------------------------------------------------
     def push_pull(self) -> None:

@@ -30,6 +30,8 @@ from typing import Dict, List, Optional, Sequence, Set, Tuple
 import torch
 import torch.distributed as dist
 
+from ..ops.grad_stage import GradStage
+from ..utils.tracing import trace_range
 from .sharding import ShardPlan
 from .ps import ParameterServer
 from . import mailbox as mbox
@@ -148,6 +150,77 @@ def _stream_ctx(s):
 
 
 # ------------------------------------------------------------------------------------------
+# the exchange interface
+# ------------------------------------------------------------------------------------------
+class Exchange:
+    """Everything the trainer, the checkpoints and the benchmark ask of an exchange.  The step is
+    ``accumulate()`` for every micro-batch but the last and ``step()`` for the last, which
+    exchanges, clips and updates; the lifecycle hooks default to nothing, so a caller never asks
+    an exchange what it is.  A subclass either hands the step to a native runner (and overrides
+    ``step`` / ``accumulate``) or inherits the host-driven body below and supplies the exchange
+    that ends it: ``finish_step()`` (sync) or ``push_pull()`` (async)."""
+
+    native = False        # the whole step runs in a C++ runner
+    backend = None        # the data plane's name, where there is a choice ("rccl", "xgmi", ..)
+    runner = None         # the native step runner, if any
+    service_mode = None   # async: who applies the pushes ("host", "inline")
+    steps = 0             # async: the pushes every worker will make in this run
+    on_segment = None     # the engine's per-segment callback of a host-driven step
+
+    def __init__(self, engine=None, stage: Optional[GradStage] = None):
+        self.engine = engine
+        self.stage = stage or GradStage()  # clip and accumulation (default: both off)
+
+    # -- the step ----------------------------------------------------------------------------------
+    def step(self, x, y, keep_prob: float, seed: int) -> None:
+        self._micro(x, y, keep_prob, seed, True)
+
+    def accumulate(self, x, y, keep_prob: float, seed: int) -> None:
+        self._micro(x, y, keep_prob, seed, False)
+
+    def _micro(self, x, y, keep_prob: float, seed: int, final: bool) -> None:
+        """One micro-batch of a step the host drives: the backward, the accumulate pass, and after
+        the step's last one the clip and the class's own exchange."""
+        stage = self.stage
+        if stage.done == 0:
+            self.begin_step()  # one apply_gradients per step, not per micro-batch
+        with trace_range("fwd_bwd"):
+            self.engine.forward_backward(x, y, keep_prob, seed, on_segment=self.on_segment)
+        stage.after_micro(self.grads)
+        if final:
+            stage.finish(self.grads)
+            self._end_step()
+
+    def _native_args(self, x, y, keep_prob: float, seed: int):
+        """What a native runner's step takes, from what the trainer hands over."""
+        self.engine._set_keep(keep_prob)
+        return x if x.is_contiguous() else x.contiguous(), y, seed & 0xFFFFFFFF
+
+    def _end_step(self) -> None:
+        with trace_range("push_pull"):
+            self.push_pull()
+
+    # -- the lifecycle: nothing to do unless a subclass says otherwise ------------------------------
+    def _nothing(self) -> None:
+        pass
+
+    begin_step = _nothing         # the first micro-batch of a host-driven step is about to run
+    start = _nothing            # async: start serving this run's `steps` pushes per worker
+    join = _nothing               # async: every expected push applied, the last round back
+    verify_provenance = _nothing  # async, after join(): every push applied once, in order
+    drain_round = _nothing        # checkpoint: a round in flight has come back
+    check = _nothing              # raise if the data plane recorded an asynchronous error
+    sync_ps_state = _nothing      # checkpoint: optimizer state the exchange holds -> the PS objects
+    load_ps_state = _nothing      # resume: the PS objects' restored state -> the exchange's own
+    abort = _nothing              # watchdog: make blocked collectives return
+    close = _nothing              # release what is held outside Python (every rank, same point)
+
+    def paused(self):
+        """Checkpoint hook: a context in which no PS update is issued."""
+        return contextlib.nullcontext()
+
+
+# ------------------------------------------------------------------------------------------
 # sync exchange
 # ------------------------------------------------------------------------------------------
 @dataclass
@@ -175,15 +248,18 @@ def quirk_coefficient(plan: ShardPlan, rank: int, world: int, ref_quirks: bool) 
     return float(2 ** (world - 1)) if rank == world - 1 else 0.0
 
 
-class SyncExchange:
+class SyncExchange(Exchange):
     uses_side = True
 
     def __init__(self, plan: ShardPlan, env: DistEnv, params: torch.Tensor,
                  grads: torch.Tensor, segments: Sequence[Sequence[int]],
                  servers: Dict[int, ParameterServer], grad_reduce: str = "sum",
                  ref_quirks: bool = False, overlap: bool = True, group=None,
-                 force_collectives: bool = False):
+                 force_collectives: bool = False, engine=None, stage: Optional[GradStage] = None):
+        Exchange.__init__(self, engine, stage)
         self.plan, self.env = plan, env
+        # a clipped or accumulated step hands nothing over per segment
+        self.on_segment = None if self.stage.whole else self.grads_ready
         # W = 1 normally updates locally; forcing keeps the collective unit kinds (run by the
         # native runner on a 1-rank RCCL communicator: the exchange path tested on one GPU)
         self.collective = env.world > 1 or force_collectives
@@ -334,11 +410,83 @@ class SyncExchange:
         if self.side is not None:
             torch.cuda.current_stream(self.params.device).wait_stream(self.side)
 
+    def _end_step(self) -> None:
+        with trace_range("exchange"):
+            self.finish_step()
+
 
 # ------------------------------------------------------------------------------------------
 # async exchange
 # ------------------------------------------------------------------------------------------
-class AsyncExchange:
+class AsyncBase(Exchange):
+    """What the three asynchronous data planes share: the plan check, the PS ranges and hosts, the
+    expected push count, the step-counter mirror and the provenance check.  Where they differ it
+    is data on the class."""
+
+    unavailable: type = ValueError  # raised for a plan or a set-up this data plane cannot run
+    plan_hint = ""                  # appended to the plan check's message
+    serves_self = False             # this rank's own pushes go through the PS service too
+    records_self = True             # ... and are recorded in the provenance
+    round_base = 0                  # a worker's first round as the native service numbers it
+    grad_scale = 1.0                # the async PS applies each worker's gradient as-is
+
+    def __init__(self, plan: ShardPlan, env: DistEnv, params: torch.Tensor, grads: torch.Tensor,
+                 servers: Dict[int, ParameterServer], steps_per_worker: int,
+                 check_provenance: bool, engine=None, stage: Optional[GradStage] = None):
+        P, W = plan.num_ps, env.world
+        for p in range(P):
+            if len(plan.ps_segments(p)) != 1:
+                raise self.unavailable("async mode needs one contiguous range per PS"
+                                       + self.plan_hint)
+        Exchange.__init__(self, engine, stage)
+        self.plan, self.env, self.params, self.grads = plan, env, params, grads
+        self.servers = servers
+        self.steps = steps_per_worker
+        self.ranges: List[Tuple[int, int]] = [plan.ps_segments(p)[0] for p in range(P)]
+        self.hosts = [plan.host_rank(p, W) for p in range(P)]
+        self.served = 0
+        # (worker, ps, that worker's round from 0, the PS's step counter) per applied push
+        self.check_provenance = check_provenance
+        self.provenance: List[Tuple[int, int, int, int]] = []
+
+    def _expected(self) -> int:
+        """The pushes this rank's PS service will see in this run."""
+        workers = self.env.world if self.serves_self else self.env.world - 1
+        return self.hosts.count(self.env.rank) * workers * self.steps
+
+    def _sync_counters(self, t_of) -> None:
+        """A native service or runner advances each hosted PS's step counter (``t_of(ps)``);
+        mirror it into the ParameterServer objects (checkpoints and reports read those)."""
+        for p, ps in self.servers.items():
+            n = t_of(p) - ps.t
+            ps.t += n
+            ps.updates += n
+
+    def _collect(self, t_of, served: int, provenance) -> None:
+        """At the end of a run: the counters, the pushes served and, if recorded, the provenance
+        with rounds counted from 0."""
+        self._sync_counters(t_of)
+        self.served = served
+        if self.check_provenance:
+            self.provenance = [(w, p, k - self.round_base, t) for (w, p, k, t) in provenance()]
+
+    def verify_provenance(self) -> None:
+        """After join(): every hosted PS applied exactly `steps` pushes of every worker whose
+        pushes it records, each once, in step order, and its step counter advanced once per
+        push."""
+        for p in self.servers:
+            for w in range(self.env.world):
+                if w == self.env.rank and not self.records_self:
+                    continue
+                steps = [s for (ww, pp, s, _) in self.provenance if ww == w and pp == p]
+                if steps != list(range(self.steps)):
+                    raise RuntimeError(f"provenance: PS {p} / worker {w} steps {steps[:5]}...")
+            ts = [t for (_, pp, _, t) in self.provenance if pp == p]
+            if ts != sorted(ts) or len(set(ts)) != len(ts):
+                raise RuntimeError(f"provenance: PS {p} step counter not strictly increasing")
+
+
+class AsyncExchange(AsyncBase):
     """Lock-free asynchronous PS over point-to-point RCCL.
 
     Worker side (``push_pull``): for each PS p in order — post ``(rank, p)`` to the
@@ -355,23 +503,19 @@ class AsyncExchange:
     the service thread never share a communicator's op order.
     """
 
+    plan_hint = " (use a tensor-granular plan or an unbucketed flat plan)"
+    records_self = False  # local pushes bypass the service
+
     def __init__(self, plan: ShardPlan, env: DistEnv, params: torch.Tensor, grads: torch.Tensor,
                  servers: Dict[int, ParameterServer], steps_per_worker: int,
                  grad_reduce: str = "sum", mailbox_kind: str = "auto", job_id: str = "ddl",
-                 check_provenance: bool = False):
-        for p in range(plan.num_ps):
-            if len(plan.ps_segments(p)) != 1:
-                raise ValueError("async mode needs one contiguous range per PS "
-                                 "(use a tensor-granular plan or an unbucketed flat plan)")
+                 check_provenance: bool = False, engine=None, stage=None):
+        super().__init__(plan, env, params, grads, servers, steps_per_worker, check_provenance,
+                         engine, stage)
         if env.world > 1 and params.is_cuda and env.backend != "nccl":
             # gloo has no GPU send/recv: the RCCL pair path needs the nccl (RCCL) backend
             raise RuntimeError("async RCCL-pair exchange needs the nccl backend for GPU tensors "
                                "(with several ranks on one GPU use --exchange xgmi)")
-        self.plan, self.env = plan, env
-        self.params, self.grads = params, grads
-        self.servers = servers
-        self.steps = steps_per_worker
-        self.grad_scale = 1.0  # async PS applies each worker's gradient as-is
         W, r = env.world, env.rank
         self.pair_groups: Dict[Tuple[int, int], object] = {}
         if W > 1:
@@ -384,37 +528,29 @@ class AsyncExchange:
         store = dist.distributed_c10d._get_default_store() if W > 1 else None
         self.mailbox = None
         if W > 1:
-            hosted = [p for p in range(plan.num_ps) if plan.host_rank(p, W) == r]
             name = f"{job_id}_mbox_{r}"
-            self.mailbox = mbox.make_mailbox(mailbox_kind, store, name, owner=True) if hosted else None
+            self.mailbox = (mbox.make_mailbox(mailbox_kind, store, name, owner=True)
+                            if r in self.hosts else None)
             dist.barrier()
             self.remote_boxes = {}
             for h in range(W):
-                if h != r and any(plan.host_rank(p, W) == h for p in range(plan.num_ps)):
+                if h != r and h in self.hosts:
                     self.remote_boxes[h] = mbox.make_mailbox(mailbox_kind, store, f"{job_id}_mbox_{h}",
                                                              owner=False)
         for ps in servers.values():
             ps.gbuf = torch.empty(ps.numel, dtype=torch.float32, device=params.device)
         self._thread: Optional[threading.Thread] = None
         self._error: Optional[BaseException] = None
-        self.served = 0
         # Race detection: with check_provenance every push carries a
         # (step, fp64 checksum) header; the PS verifies that the bytes it applies are exactly
         # what that worker pushed for that step, that each worker's pushes to a PS arrive in
         # order with none lost or duplicated, and logs (worker, ps, step, t) per update.
-        self.check_provenance = check_provenance
-        self.provenance: List[Tuple[int, int, int, int]] = []
         self._last_step: Dict[Tuple[int, int], int] = {}
         self._push_step: Dict[int, int] = {}
 
     # -- PS service thread -------------------------------------------------------------------------
-    def _expected_remote(self) -> int:
-        W, r = self.env.world, self.env.rank
-        n_hosted = sum(1 for p in range(self.plan.num_ps) if self.plan.host_rank(p, W) == r)
-        return n_hosted * (W - 1) * self.steps
-
     def start(self) -> None:
-        if self.env.world == 1 or self._expected_remote() == 0:
+        if self.env.world == 1 or self._expected() == 0:
             return
         self._thread = threading.Thread(target=self._serve, name="ps-service", daemon=True)
         self._thread.start()
@@ -426,7 +562,7 @@ class AsyncExchange:
             if stream is not None:
                 torch.cuda.set_device(dev)
             with _stream_ctx(stream):
-                for _ in range(self._expected_remote()):
+                for _ in range(self._expected()):
                     v = self.mailbox.pop(600.0)
                     if v is None:
                         raise TimeoutError("async PS: no arrival within 600 s")
@@ -461,20 +597,6 @@ class AsyncExchange:
                                f"{last} (lost, duplicated or reordered push)")
         self._last_step[(w, p)] = step
 
-    def verify_provenance(self) -> None:
-        """After join(): every hosted PS applied exactly `steps` pushes of every remote
-        worker, each once, in step order, and its step counter advanced once per push."""
-        for p, ps in self.servers.items():
-            for w in range(self.env.world):
-                if w == self.env.rank:
-                    continue
-                steps = [s for (ww, pp, s, _) in self.provenance if ww == w and pp == p]
-                if steps != list(range(self.steps)):
-                    raise RuntimeError(f"provenance: PS {p} / worker {w} steps {steps[:5]}...")
-            ts = [t for (_, pp, _, t) in self.provenance if pp == p]
-            if ts != sorted(ts) or len(set(ts)) != len(ts):
-                raise RuntimeError(f"provenance: PS {p} step counter not strictly increasing")
-
     @contextlib.contextmanager
     def paused(self):
         """Checkpoint hook: the service thread updates a PS only under its lock (on its
@@ -496,10 +618,8 @@ class AsyncExchange:
 
     # -- worker side ----------------------------------------------------------------------------------
     def push_pull(self) -> None:
-        W, r = self.env.world, self.env.rank
-        for p in range(self.plan.num_ps):
-            host = self.plan.host_rank(p, W)
-            (lo, hi), = self.plan.ps_segments(p)
+        r = self.env.rank
+        for p, (host, (lo, hi)) in enumerate(zip(self.hosts, self.ranges)):
             if host == r:
                 ps = self.servers[p]
                 with ps.exclusive():

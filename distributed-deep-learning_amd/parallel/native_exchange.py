@@ -30,7 +30,6 @@ on ONE GPU (gloo default group) — the multi-process rehearsal of the W > 1 ste
 from __future__ import annotations
 
 import os
-import sys
 from typing import Dict, Sequence
 
 import torch
@@ -38,6 +37,7 @@ import torch.distributed as dist
 
 from ..ops import native
 from ..ops.adam import adam_coeffs
+from ..utils.tracing import trace_range
 from .comm import DistEnv, SyncExchange, agree
 from .ps import ParameterServer
 from .sharding import ShardPlan
@@ -81,8 +81,7 @@ class NativeSyncExchange(SyncExchange):
                  grad_reduce: str = "sum", ref_quirks: bool = False, overlap: bool = True,
                  optimizer: str = "adam", hyper=None, momentum: float = 0.9,
                  force_collectives: bool = False, backend: str = "rccl",
-                 weight_decay: float = 0.0, nesterov: bool = False, clip=None,
-                 accum=None):
+                 weight_decay: float = 0.0, nesterov: bool = False, stage=None):
         if optimizer not in ("adam", "momentum", "sgd"):
             raise NativeUnavailable(f"native runner has no '{optimizer}' update")
         if optimizer == "sgd":
@@ -93,8 +92,8 @@ class NativeSyncExchange(SyncExchange):
         if len(segments) != 4:
             raise NativeUnavailable("native runner expects the engine's 4 backward segments")
         super().__init__(plan, env, params, grads, segments, servers, grad_reduce, ref_quirks,
-                         overlap=overlap, force_collectives=force_collectives)
-        self.engine = engine
+                         overlap=overlap, force_collectives=force_collectives, engine=engine,
+                         stage=stage)
         self.optimizer = optimizer
         ops = native.ops()
         # The step's LAST bucket (conv2 + conv1, 52 k parameters) completes with the backward, so
@@ -174,19 +173,15 @@ class NativeSyncExchange(SyncExchange):
                                   momentum, weight_decay, nesterov)
         self.runner.set_units(units)
         self.runner.set_scale(self.grad_scale, self.coef)
-        # clip = (max_norm, [(lo, n)] payload ranges, the {norm, coef} buffer): the runner clips
-        # after the fourth backward segment (the caller passed overlap=False: every unit above
-        # is the last segment's)
-        if clip is not None:
-            if overlap:
-                raise ValueError("a clipped step has no per-segment hand-off: overlap=False")
-            self.runner.set_clip(*clip)
-        # accum = (K, [(lo, n)] payload ranges, the accumulator): K - 1 accumulate() calls, then
-        # step(), whose final micro-batch runs as a clipped step does (overlap=False again)
-        if accum is not None:
-            if overlap:
-                raise ValueError("an accumulated step has no per-segment hand-off: overlap=False")
-            self.runner.set_accum(*accum)
+        # the stage's clip triple: the runner clips after the fourth backward segment (the caller
+        # passed overlap=False: every unit above is the last segment's); its accumulation triple:
+        # K - 1 accumulate() calls, then step(), whose final micro-batch runs as a clipped step
+        # does (overlap=False again)
+        if overlap and self.stage.clip is not None:
+            raise ValueError("a clipped step has no per-segment hand-off: overlap=False")
+        if overlap and self.stage.accum is not None:
+            raise ValueError("an accumulated step has no per-segment hand-off: overlap=False")
+        self.stage.attach(self.runner)
         # A/B knob: DDL_LAST_ON_MAIN=0 puts the last segment's collectives back on the comm
         # stream (one event hop more on the critical path of every W > 1 step)
         self.runner.set_last_on_main(os.environ.get("DDL_LAST_ON_MAIN", "1") != "0")
@@ -310,13 +305,12 @@ class NativeSyncExchange(SyncExchange):
         """One synchronous global step: every hosted PS advances its step counter (one
         ``apply_gradients`` per global step, like the reference PS) and the runner enqueues
         compute + exchange + update."""
-        eng = self.engine
-        eng._set_keep(keep_prob)
         lr = self._lr
         for p, ps in self.servers.items():
             ps.begin()
             lr[p] = adam_coeffs(ps.h, ps.t) if self.optimizer == "adam" else ps.h.lr
-        self.runner.step(x if x.is_contiguous() else x.contiguous(), labels, seed & 0xFFFFFFFF, lr)
+        with trace_range("step_native"):
+            self.runner.step(*self._native_args(x, labels, keep_prob, seed), lr)
         self._n += 1
         if self.env.world > 1 and self._n % 64 == 0:
             self.check()
@@ -325,9 +319,8 @@ class NativeSyncExchange(SyncExchange):
                    seed: int) -> None:
         """A non-final micro-batch of an accumulated step: forward, backward and the
         accumulate pass.  No PS counter advances and nothing is exchanged or updated."""
-        self.engine._set_keep(keep_prob)
-        self.runner.accumulate(x if x.is_contiguous() else x.contiguous(), labels,
-                               seed & 0xFFFFFFFF)
+        with trace_range("step_native"):
+            self.runner.accumulate(*self._native_args(x, labels, keep_prob, seed))
 
     # -- the READY-flag hand-off, proven per job (VERDICT r4 item 4) ------------------------------
     def _snapshot(self):
@@ -476,31 +469,3 @@ def handoff_vote(env, digest_events: str, digest_flags: str) -> dict:
             f"refusing this data plane")
     return {"ok": modes_agree and ranks_agree, "modes_agree": modes_agree,
             "ranks_agree": ranks_agree}
-
-
-def make_sync_exchange(plan, env, params, grads, segments, servers, engine, cfg, hyper,
-                       clip=None, accum=None):
-    """Native runner when it applies (HIP engine, sync, adam/momentum/sgd), else the Python
-    exchange.  On a multi-GPU job the choice is collective (self-test votes).  clip: the
-    trainer's (max_norm, ranges, out) when --clip-norm is on; the native runner then clips
-    itself, the Python exchange's caller clips between the backward and finish_step().  Either
-    way nothing is handed over per segment (overlap off).  accum: the trainer's (K, ranges,
-    accumulator) when --accum-steps is above 1, handed through in the same way: the native
-    runner accumulates itself, the Python exchange's caller between the backward and
-    finish_step(), and overlap is off."""
-    overlap = cfg.overlap and clip is None and accum is None
-    if cfg.native_exchange:
-        try:
-            backend = cfg.exchange_backend if cfg.exchange_backend != "auto" else "rccl"
-            return NativeSyncExchange(plan, env, params, grads, segments, servers, engine,
-                                      cfg.grad_reduce, cfg.ref_quirks, overlap,
-                                      cfg.optimizer, hyper, cfg.momentum,
-                                      force_collectives=cfg.force_collectives, backend=backend,
-                                      weight_decay=cfg.weight_decay, nesterov=cfg.nesterov,
-                                      clip=clip, accum=accum)
-        except NativeUnavailable as e:
-            if env.rank == 0 and getattr(engine, "name", "") == "hip":
-                print(f"[ddl_amd] native sync runner unavailable ({e}); using the Python "
-                      f"exchange", file=sys.stderr)
-    return SyncExchange(plan, env, params, grads, segments, servers, cfg.grad_reduce,
-                        cfg.ref_quirks, overlap=overlap)

@@ -27,16 +27,16 @@ from ..models import make_engine, engine_segments
 from ..models.mnist_cnn import init_params_
 from ..ops import rng
 from ..ops import clip as clip_ops
-from ..ops import accum as accum_ops
 from ..ops import shuffle as shuffle_ops
 from ..ops.adam import AdamHyper
+from ..ops.grad_stage import GradStage
 from ..utils import metrics
 from ..utils.data import Dataset, get_dataset, batch_indices
 from ..utils.watchdog import Watchdog
 from ..utils import checkpoint as ckpt
 from ..utils.tracing import trace_range
 from .comm import DistEnv, SyncExchange, AsyncExchange, init_distributed
-from .native_exchange import make_sync_exchange
+from .native_exchange import NativeSyncExchange, NativeUnavailable
 from .ps import ParameterServer
 from .sharding import async_groups, make_plan, segment_aligned_num_ps
 
@@ -57,6 +57,73 @@ def resolve_num_ps(cfg: TrainConfig, world: int) -> int:
     if cfg.mode == "single" or cfg.shard == "none":
         return 1
     return cfg.num_ps or world
+
+
+def make_exchange(cfg: TrainConfig, env: DistEnv, plan, params, grads, segments, servers, engine,
+                  hyper, stage: GradStage, asyncx: bool, steps: int):
+    """The exchange of a trainer, with both fallback chains.  stage: the trainer's clip and
+    accumulation; a native runner takes its triples, a host-driven step calls it.
+
+    Sync (and async run as sync): the native runner when it applies (HIP engine,
+    adam/momentum/sgd), else the Python exchange; on a multi-GPU job the choice is collective
+    (self-test votes).  A clipped or accumulated step hands nothing over per segment (overlap
+    off).
+
+    Async.  On a GPU: the xGMI peer-memory exchange (``async_xgmi.py``, no p2p kernels at all)
+    when asked for, or by default at W > 1 with the HIP engine; else point-to-point RCCL in
+    exclusive sessions (``async_rccl.py``, deadlock-free under any stream-to-hardware-queue
+    mapping).  The round-2 Python RCCL pair-group exchange, whose concurrent p2p kernels could
+    block each other's hardware queues, is NOT a GPU fallback any more; it remains the CPU (gloo)
+    implementation.  ``steps``: the pushes every worker makes in a whole run."""
+    if not asyncx:
+        overlap = cfg.overlap and not stage.whole
+        if cfg.native_exchange:
+            try:
+                backend = cfg.exchange_backend if cfg.exchange_backend != "auto" else "rccl"
+                return NativeSyncExchange(plan, env, params, grads, segments, servers, engine,
+                                          cfg.grad_reduce, cfg.ref_quirks, overlap,
+                                          cfg.optimizer, hyper, cfg.momentum,
+                                          force_collectives=cfg.force_collectives,
+                                          backend=backend, weight_decay=cfg.weight_decay,
+                                          nesterov=cfg.nesterov, stage=stage)
+            except NativeUnavailable as e:
+                if env.rank == 0 and engine.name == "hip":
+                    print(f"[ddl_amd] native sync runner unavailable ({e}); using the Python "
+                          f"exchange", file=sys.stderr)
+        return SyncExchange(plan, env, params, grads, segments, servers, cfg.grad_reduce,
+                            cfg.ref_quirks, overlap=overlap, engine=engine, stage=stage)
+    job = _job_id(env)
+    cuda = env.device.type == "cuda"
+    common = dict(steps_per_worker=steps, check_provenance=cfg.check_provenance, job_id=job,
+                  engine=engine, stage=stage)
+    want_xgmi = cfg.exchange_backend == "xgmi" or (
+        cfg.exchange_backend == "auto" and env.world > 1 and engine.name == "hip")
+    if want_xgmi and cuda:
+        from .async_xgmi import AsyncPeerExchange, AsyncPeerUnavailable
+        try:
+            ex = AsyncPeerExchange(plan, env, params, grads, servers, grad_reduce=cfg.grad_reduce,
+                                   optimizer=cfg.optimizer, **common)
+        except AsyncPeerUnavailable as e:
+            if env.rank == 0:
+                print(f"[ddl_amd] async xGMI exchange unavailable ({e}); using RCCL sessions",
+                      file=sys.stderr)
+        else:
+            ex.attach_runner(segments)  # (the native worker step, with the HIP engine)
+            return ex
+    if cuda:
+        from .async_rccl import RcclAsyncExchange, RcclAsyncUnavailable
+        try:
+            return RcclAsyncExchange(plan, env, params, grads, servers, optimizer=cfg.optimizer,
+                                     **common)
+        except RcclAsyncUnavailable as e:
+            if env.world > 1 and env.backend == "nccl":
+                raise RuntimeError(f"async mode on GPU: neither the xGMI nor the RCCL-"
+                                   f"session exchange is available ({e})") from e
+            # a non-RCCL default group (the shared-GPU gloo rehearsal after an xGMI set-up
+            # failure) keeps the host-driven exchange, as before round 3
+            print(f"[ddl_amd] async RCCL-session exchange unavailable ({e}); using the "
+                  f"host-driven exchange", file=sys.stderr)
+    return AsyncExchange(plan, env, params, grads, servers, grad_reduce=cfg.grad_reduce, **common)
 
 
 class Trainer:
@@ -86,6 +153,8 @@ class Trainer:
         # the W = 1 rehearsals of the async data planes).
         self.async_as_sync = (asyncm and W == 1 and not cfg.ref_quirks
                               and cfg.exchange_backend == "auto")
+        # ... so the run has an asynchronous data plane (PS services, private PS copies) only here
+        self.asyncx = asyncm and not self.async_as_sync
         sync_step = cfg.mode == "sync" or self.async_as_sync
         buckets = segs if (cfg.shard == "flat" and cfg.overlap and sync_step) else None
         shard = "none" if cfg.mode == "single" else cfg.shard
@@ -93,8 +162,7 @@ class Trainer:
         # right after its segment and only the last segment's (52 K-element) shards remain on
         # the step's critical path; needs a PS per segment (P a multiple of W with balanced
         # hosts unless --num-ps sets it, sharding.segment_aligned_num_ps).
-        aligned = (asyncm and not self.async_as_sync and cfg.shard == "flat" and cfg.overlap
-                   and len(segs) > 1)
+        aligned = self.asyncx and cfg.shard == "flat" and cfg.overlap and len(segs) > 1
         if aligned:
             groups = async_groups(segs)
             self.num_ps = cfg.num_ps or segment_aligned_num_ps(W, groups)
@@ -118,7 +186,7 @@ class Trainer:
         self.servers: Dict[int, ParameterServer] = {}
         for p in hosted:
             own = None
-            if asyncm and not self.async_as_sync:
+            if self.asyncx:
                 own = self.params
                 if cfg.ref_quirks:  # PS initialised independently of the workers (Q4)
                     tmp = torch.zeros_like(self.params)
@@ -149,69 +217,22 @@ class Trainer:
         self.clip_ranges = clip_ops.payload_ranges(self.plan.tensor_offsets)
         self.clip_out = (torch.zeros(2, dtype=torch.float32, device=dev)  # {norm, coef}
                          if cfg.clip_norm > 0 else None)
-        clip = (cfg.clip_norm, self.clip_ranges, self.clip_out) if cfg.clip_norm > 0 else None
         # Accumulation over K micro-batches (ops/accum.py, csrc/kernels/accum.hip): the sum stays
         # in an fp32 buffer of the gradient buffer's size, allocated once; after the last
         # micro-batch the gradient buffer holds the mean and everything downstream reads it.
         # Like a clipped step, the final micro-batch hands nothing over per segment.
         self.accum_buf = torch.zeros_like(self.grads) if K > 1 else None
-        accum = (K, self.clip_ranges, self.accum_buf) if K > 1 else None
-        if asyncm and not self.async_as_sync:
-            self.exchange = self._make_async_exchange(cfg, env)
-            if hasattr(self.exchange, "attach_runner"):
-                self.exchange.attach_runner(self.engine, segs, accum=accum)
-                if clip is not None and self.exchange.runner is not None:
-                    self.exchange.runner.set_clip(*clip)
-        else:
-            self.exchange = make_sync_exchange(self.plan, env, self.params, self.grads, segs,
-                                               self.servers, self.engine, cfg, hyper, clip=clip,
-                                               accum=accum)
+        # one stage for whichever exchange is built: a native runner takes its triples, a
+        # host-driven step calls it between the backward and the exchange
+        stage = GradStage(
+            clip=(cfg.clip_norm, self.clip_ranges, self.clip_out) if cfg.clip_norm > 0 else None,
+            accum=(K, self.clip_ranges, self.accum_buf) if K > 1 else None)
+        self.exchange = make_exchange(cfg, env, self.plan, self.params, self.grads, segs,
+                                      self.servers, self.engine, hyper, stage,
+                                      asyncx=self.asyncx, steps=self.steps * cfg.epochs)
         self.log = metrics.JsonlLogger(cfg.log_jsonl, r)
         self.global_step = 0
         self.history: List[dict] = []
-
-    def _make_async_exchange(self, cfg: TrainConfig, env: DistEnv):
-        """The async data plane.  On a GPU: the xGMI peer-memory exchange (``async_xgmi.py``,
-        no p2p kernels at all) when asked for, or by default at W > 1 with the HIP engine; else
-        point-to-point RCCL in exclusive sessions (``async_rccl.py``, deadlock-free under any
-        stream-to-hardware-queue mapping).  The round-2 Python RCCL pair-group exchange, whose
-        concurrent p2p kernels could block each other's hardware queues, is NOT a GPU fallback
-        any more; it remains the CPU (gloo) implementation."""
-        steps = self.steps * cfg.epochs
-        job = _job_id(env)
-        cuda = env.device.type == "cuda"
-        want_xgmi = cfg.exchange_backend == "xgmi" or (
-            cfg.exchange_backend == "auto" and env.world > 1 and self.engine.name == "hip")
-        import sys
-        if want_xgmi and cuda:
-            from .async_xgmi import AsyncPeerExchange, AsyncPeerUnavailable
-            try:
-                return AsyncPeerExchange(self.plan, env, self.params, self.grads, self.servers,
-                                         steps_per_worker=steps, grad_reduce=cfg.grad_reduce,
-                                         check_provenance=cfg.check_provenance,
-                                         optimizer=cfg.optimizer, job_id=job)
-            except AsyncPeerUnavailable as e:
-                if env.rank == 0:
-                    print(f"[ddl_amd] async xGMI exchange unavailable ({e}); using RCCL sessions",
-                          file=sys.stderr)
-        if cuda:
-            from .async_rccl import RcclAsyncExchange, RcclAsyncUnavailable
-            try:
-                return RcclAsyncExchange(self.plan, env, self.params, self.grads, self.servers,
-                                         steps_per_worker=steps, job_id=job,
-                                         optimizer=cfg.optimizer,
-                                         check_provenance=cfg.check_provenance)
-            except RcclAsyncUnavailable as e:
-                if env.world > 1 and env.backend == "nccl":
-                    raise RuntimeError(f"async mode on GPU: neither the xGMI nor the RCCL-"
-                                       f"session exchange is available ({e})") from e
-                # a non-RCCL default group (the shared-GPU gloo rehearsal after an xGMI set-up
-                # failure) keeps the host-driven exchange, as before round 3
-                print(f"[ddl_amd] async RCCL-session exchange unavailable ({e}); using the "
-                      f"host-driven exchange", file=sys.stderr)
-        return AsyncExchange(self.plan, env, self.params, self.grads, self.servers,
-                             steps_per_worker=steps, grad_reduce=cfg.grad_reduce,
-                             check_provenance=cfg.check_provenance, job_id=job)
 
     # ---- one worker step (reference SyncWorker.work + pull + assign) -----------------------------
     def batch(self, step: int, epoch: Optional[int] = None):
@@ -241,85 +262,22 @@ class Trainer:
             shuffle_ops.assemble_batch(*args)
         return self.batch_x, self.batch_y
 
-    def clip_grads(self) -> None:
-        """Clip this worker's gradient buffer in place (the Python-driven step paths); the
-        norm and the coefficient stay in ``clip_out``."""
-        if self.grads.is_cuda:
-            from ..ops import native
-            native.ops().clip_grads(self.grads, self.clip_ranges, self.cfg.clip_norm,
-                                    self.clip_out)
-        else:
-            norm, coef = clip_ops.clip_grads_(self.grads, self.clip_ranges, self.cfg.clip_norm)
-            self.clip_out[0], self.clip_out[1] = norm, coef
-
     def last_grad_norm(self) -> Optional[float]:
         """The global norm of the last step's gradient before clipping (None with clipping
         off).  Reads the device buffer: call it where the trainer synchronises anyway."""
         return None if self.clip_out is None else float(self.clip_out[0])
-
-    def accum_grads(self, j: int) -> None:
-        """The accumulation pass after micro-batch ``j`` of the step (the Python-driven step
-        paths): the sum into ``accum_buf``, after the last one the mean into ``grads``."""
-        K = self.cfg.accum_steps
-        mode = accum_ops.mode_of(j, K)
-        if self.grads.is_cuda:
-            from ..ops import native
-            native.ops().accum_grads(self.grads, self.accum_buf, self.clip_ranges, mode, K)
-        else:
-            accum_ops.accum_grads_(self.grads, self.accum_buf, self.clip_ranges, mode, K)
 
     def train_step(self, step: int) -> None:
         """One step = one update, from ``accum_steps`` micro-batches: micro-batch ``j`` of
         step index ``step`` reads batch ``step * K + j`` with the dropout seed of micro-step
         ``global_step * K + j`` (K = 1: the step's own).  Only the last one exchanges, clips
         and updates; the others leave their gradient in the accumulator."""
-        cfg = self.cfg
-        clip = self.clip_out is not None
+        cfg, ex = self.cfg, self.exchange
         K = cfg.accum_steps
-        ex = self.exchange
         for j in range(K):
-            final = j == K - 1
             x, y = self.batch(step * K + j)
             seed = rng.step_seed(cfg.seed, self.env.rank, self.global_step * K + j)
-            if cfg.mode == "async" and not self.async_as_sync and \
-                    getattr(ex, "runner", None) is not None:
-                with trace_range("step_native_async"):
-                    if final:
-                        ex.native_step(self.engine, x, y, cfg.keep_prob, seed)
-                    else:
-                        ex.native_accumulate(self.engine, x, y, cfg.keep_prob, seed)
-            elif cfg.mode == "async" and not self.async_as_sync:
-                with trace_range("fwd_bwd"):
-                    self.engine.forward_backward(x, y, cfg.keep_prob, seed)
-                if K > 1:
-                    self.accum_grads(j)
-                if not final:
-                    continue
-                if clip:
-                    self.clip_grads()
-                with trace_range("push_pull"):
-                    ex.push_pull()
-            elif getattr(ex, "native", False):
-                with trace_range("step_native"):
-                    if final:
-                        ex.step(x, y, cfg.keep_prob, seed)
-                    else:
-                        ex.accumulate(x, y, cfg.keep_prob, seed)
-            else:
-                if j == 0:
-                    ex.begin_step()  # one apply_gradients per step, not per micro-batch
-                with trace_range("fwd_bwd"):
-                    self.engine.forward_backward(
-                        x, y, cfg.keep_prob, seed,
-                        on_segment=None if (clip or K > 1) else ex.grads_ready)
-                if K > 1:
-                    self.accum_grads(j)
-                if not final:
-                    continue
-                if clip:
-                    self.clip_grads()
-                with trace_range("exchange"):
-                    ex.finish_step()
+            (ex.step if j == K - 1 else ex.accumulate)(x, y, cfg.keep_prob, seed)
         self.global_step += 1
 
     def evaluate(self) -> float:
@@ -345,23 +303,20 @@ class Trainer:
         with an error instead of spinning) and end the process so the launcher tears the
         job down."""
         import os
-        import sys
         import threading
-        ab = getattr(self.exchange, "abort", None)
-        if ab is not None:
-            # ncclCommAbort can itself block (proxy threads, kernels stuck on a dead peer):
-            # run it on a daemon thread and exit unconditionally after a bounded join
-            def _abort():
-                try:
-                    ab()
-                except Exception as e:  # best effort: we are exiting anyway
-                    sys.stderr.write(f"[watchdog] comm abort failed: {e}\n")
-            t = threading.Thread(target=_abort, name="ddl-comm-abort", daemon=True)
-            t.start()
-            t.join(timeout=self.ABORT_GRACE_S)
-            if t.is_alive():
-                sys.stderr.write("[watchdog] comm abort still blocked; exiting anyway\n")
-                sys.stderr.flush()
+        # ncclCommAbort can itself block (proxy threads, kernels stuck on a dead peer):
+        # run it on a daemon thread and exit unconditionally after a bounded join
+        def _abort():
+            try:
+                self.exchange.abort()
+            except Exception as e:  # best effort: we are exiting anyway
+                sys.stderr.write(f"[watchdog] comm abort failed: {e}\n")
+        t = threading.Thread(target=_abort, name="ddl-comm-abort", daemon=True)
+        t.start()
+        t.join(timeout=self.ABORT_GRACE_S)
+        if t.is_alive():
+            sys.stderr.write("[watchdog] comm abort still blocked; exiting anyway\n")
+            sys.stderr.flush()
         os._exit(124)
 
     # ---- reference main loop -----------------------------------------------------------------------
@@ -379,8 +334,7 @@ class Trainer:
         last = cfg.epochs * self.steps
         if cfg.max_steps is not None:
             last = min(last, cfg.max_steps)
-        asyncx = cfg.mode == "async" and not self.async_as_sync
-        if asyncx:
+        if self.asyncx:
             # the PS services expect exactly this run's pushes (every worker runs the same
             # window), and resume their step counters from the checkpoint (load above)
             self.exchange.steps = max(0, last - first)
@@ -451,7 +405,7 @@ class Trainer:
             torch.cuda.current_stream().wait_stream(aeval.train_stream)
             aeval.drain()
             aeval.close()  # its streams and its eval engine's workspace, now
-        if asyncx:
+        if self.asyncx:
             self.exchange.join()
             if cfg.check_provenance:
                 self.exchange.verify_provenance()
@@ -459,7 +413,7 @@ class Trainer:
         # xGMI wait that times out records its error only when it gives up
         if env.device.type == "cuda":
             torch.cuda.synchronize()
-        if getattr(self.exchange, "native", False) and env.world > 1:
+        if env.world > 1:
             self.exchange.check()
         if env.world > 1:
             dist.barrier()
@@ -479,7 +433,7 @@ class Trainer:
         if self.clip_out is not None:
             summary["grad_norm"] = self.last_grad_norm()
         self.log.log(event="final", **summary)
-        if asyncx:
+        if self.asyncx:
             self.exchange.close()
         return summary
 
@@ -495,10 +449,7 @@ def close_trainers(trainers, env: DistEnv) -> None:
     for t in trainers:
         # native sync runners and the asynchronous data planes (xGMI / RCCL); the Python sync
         # exchange has nothing native to release
-        close = getattr(t.exchange, "close", None)
-        if close is not None and (getattr(t.exchange, "native", False)
-                                  or t.cfg.mode == "async"):
-            close()
+        t.exchange.close()
     if env.world > 1:
         dist.barrier()
 

@@ -47,30 +47,23 @@ def _name(i: int, a: int, b: int, n: int) -> str:
 
 
 def save(trainer, path: str) -> None:
-    import contextlib
     import torch.distributed as dist
     os.makedirs(path, exist_ok=True)
     env, plan = trainer.env, trainer.plan
     asyncm = trainer.cfg.mode == "async"
     ex = trainer.exchange
-    drain = getattr(ex, "drain_round", None)  # async native step: this worker's round is back
-    if drain is not None:
-        drain()
+    ex.drain_round()  # async native step: this worker's round is back
     if trainer.params.is_cuda:
         # every queued step (and its exchange kernels) must have finished, and must not have
         # failed: a checkpoint of parameters a timed-out exchange left half-updated is refused
         torch.cuda.synchronize(trainer.params.device)
-    if getattr(ex, "native", False) and hasattr(ex, "check"):
-        ex.check()
-    sync_state = getattr(ex, "sync_ps_state", None)  # replicated optimizer state -> the PS
-    if sync_state is not None:
-        sync_state()
+    ex.check()
+    ex.sync_ps_state()  # replicated optimizer state -> the PS
     # async: the PS service keeps applying other workers' pushes.  Snapshot the hosted PS
     # state (parameters, m, v and the step counter t) with the service paused, so it is one
     # consistent PS step; the pause ends before any collective below (a peer may be waiting
     # for this PS to serve its push before it reaches its own checkpoint).
-    pause = getattr(ex, "paused", None)
-    with (pause() if pause is not None else contextlib.nullcontext()):
+    with ex.paused():
         snaps = {p: _ps_snapshot(trainer, plan, ps) for p, ps in trainer.servers.items()}
     if asyncm or env.rank == 0:
         w = {}
@@ -209,6 +202,4 @@ def load(trainer, path: str) -> None:
                   "restored by policy and PS count only", file=sys.stderr)
         ps.t = int(man["ps_t"].get(str(p)) or t_resume) if same_plan else t_resume
     trainer.global_step = int(man["global_step"])
-    load_state = getattr(trainer.exchange, "load_ps_state", None)
-    if load_state is not None:  # PS chunks -> the exchange's replicated optimizer state
-        load_state()
+    trainer.exchange.load_ps_state()  # PS chunks -> the exchange's replicated optimizer state

@@ -210,14 +210,19 @@ def same_state(tr, params, servers):
     return ok
 
 
-@pytest.mark.parametrize("mode", ["sync", "single"])
+@pytest.mark.parametrize("mode", ["sync", "single", "async"])
 def test_trainer_w1_is_the_hand_loop(one_thread, mode):
     """W = 1, B = 5, K = 3, two steps: parameters and optimizer state equal three
     forward_backward calls with the micro-steps' batches and seeds, the twin's passes and the PS
     update; the same with clip_norm at half the effective gradient's norm; and K = 1 is the
-    plain loop over today's batch indices and seeds."""
+    plain loop over today's batch indices and seeds.  async: the host-driven AsyncExchange (an
+    explicit exchange backend keeps a one-worker run off the sync step path), whose one PS
+    applies each push to its private copy, the same update."""
     kw = dict(BASE, mode=mode, shard="contiguous", steps=2, batch_size=5)
+    if mode == "async":
+        kw["exchange_backend"] = "rccl"
     k1 = trainer_steps(dict(kw, accum_steps=1), 2)
+    assert type(k1.exchange).__name__ == ("AsyncExchange" if mode == "async" else "SyncExchange")
     ref1 = hand_loop(dict(kw, accum_steps=1), 1)
     assert k1.accum_buf is None and k1.steps == 2
     assert same_state(k1, ref1[0], ref1[1])

@@ -463,7 +463,7 @@ def test_step_audit_async_inline(store, data, monkeypatch, num_ps, B):
             before = state_of(tr)
             t0 = {p: ex.runner.inline_t(p) for p in tr.servers}
             xg, snap = prepare(ctx, B, {"x": x})
-            ex.native_step(tr.engine, xg, y.to(DEV), KEEP, seed)
+            ex.step(xg, y.to(DEV), KEEP, seed)
             ex.drain_round()
             torch.cuda.synchronize()
             launches = ex.runner.update_launches()
