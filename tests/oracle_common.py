@@ -1,12 +1,13 @@
 """Shared by the GPU oracle tests (helper module, not a conftest): the poison / snapshot / check
 cycle around one engine call, on any object `ctx` that offers
 
-* ``ctx.whole(name)``: the stored buffer, the first BMAX rows, halo included;
+* ``ctx.whole(name)``: the stored buffer, every row the context covers, halo included;
 * ``ctx.grads`` and ``ctx.offsets``: the flat gradient buffer and its 14 tensor offsets;
 * ``ctx.gview(i)``: gradient tensor i, shaped;
 * ``ctx.poison_grads()``: NaN into every gradient element a kernel may write.
 
-tests/test_op_oracle_gpu.py runs it around one op on a 40-row engine, tests/test_step_audit_gpu.py
+tests/test_op_oracle_gpu.py runs it around one op on a 40-row and on a 136-row engine,
+tests/test_step_audit_gpu.py
 around a whole training step of a Trainer's engine.
 """
 import torch
@@ -42,7 +43,7 @@ def host_bits(t):
 
 
 def prepare(ctx, B, inputs):
-    """Poison every float buffer and the gradients with NaN (all 40 rows, interiors only), put the
+    """Poison every float buffer and the gradients with NaN (every row, interiors only), put the
     code sentinel in rows < B and 0 in rows >= B, write the inputs of rows < B; returns the image
     argument and a snapshot of everything."""
     nan = float("nan")

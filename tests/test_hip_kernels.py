@@ -465,6 +465,9 @@ def test_graph_replay_matches_eager(setup):
 
 
 def test_eval_count(setup):
+    """These inputs get one prediction for every row (the bias noise decides the argmax), so the
+    count here does not depend on the per-row forward: tests/test_eval_audit_gpu.py checks it row
+    by row on inputs whose predictions are known."""
     eng, flat, params, grads, x, y = setup
     xe = torch.rand(1200, 784)
     ye = torch.randint(0, 10, (1200,))

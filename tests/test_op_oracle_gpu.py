@@ -14,6 +14,19 @@ with splits 1 / 3 / default and the in-launch or the separate reduce; backward_s
 and without dual launches; the eval forward (default eval configs, 9-12 on conv2-4, and
 DDL_EVAL_KMAP2=0); eval_count over three chunks; then the real-valued precision check of every
 op and the classifier head.
+
+Past 128 rows, on a second engine of 136 rows (the fc ops have M = batch: below 64 rows no 32-row
+tile is followed by another full one and the 64- and 128-row tiles are never filled; the conv
+weight gradients have K = H*H*max(batch, 32), and split counts are not monotonic in the batch):
+all 17 ops at B = 128 and 129 on the default config with the direct conv1 kernels on and off; the
+whole tile-config sweep at B = 129; backward_segment 1-3 at B = 128 and 129 and the head's
+segment 0 at B = 129; the eval forward at B = 129, with fc1 / fc2 on eval configs 0-8.  The
+exactness condition holds there too (test_op_reference_cpu.py test_exactness_condition).
+
+Measured on one MI355X (per-test durations of a whole-suite run): the 27 tests on the 136-row
+engine 3.3 s together (slowest test_ops_exact_default_config_past_128_rows[128-True], 0.52 s: it
+builds the engine and the first fp64 references), so the whole tile-config sweep stays; the 75
+tests on the 40-row engine, which the file had before, 4.1 s.
 """
 import pytest
 import torch
@@ -30,30 +43,32 @@ WIDE_INLAUNCH, WIDE_SEPARATE = 1 << 20, 1
 
 
 class Ctx:
-    """A 40-row engine on the parameters `P` (CPU fp32 tensors), and a cache of cases."""
+    """An engine of `rows` rows (40 by default) on the parameters `P` (CPU fp32 tensors), and a
+    cache of cases."""
 
-    def __init__(self, P):
+    def __init__(self, P, rows=BMAX):
         from ddl_amd.models.hip_engine import HipEngine
         self.P = P
+        self.rows = rows
         self.P64 = [p.double() for p in P]
         self.params = torch.zeros(TOTAL_NUMEL, device=DEV)
         self.grads = torch.zeros_like(self.params)
         self.offsets = CANON_OFFSETS
-        self.eng = HipEngine(self.params, self.grads, CANON_OFFSETS, batch=BMAX, graph=False,
-                             eval_chunk=BMAX, keep_prob=KEEP)
+        self.eng = HipEngine(self.params, self.grads, CANON_OFFSETS, batch=rows, graph=False,
+                             eval_chunk=rows, keep_prob=KEEP)
         # in place: the engine holds pointers into the flat tensor
         self.params.copy_(torch.cat([p.reshape(-1) for p in P]))
         self.seed_t = torch.tensor([SEED], dtype=torch.int32, device=DEV)
-        self.labels = torch.zeros(BMAX, dtype=torch.int64, device=DEV)
+        self.labels = torch.zeros(rows, dtype=torch.int64, device=DEV)
         self.cases = {}
 
     def e(self):
         return self.eng.eng
 
     def whole(self, name):
-        """The stored buffer, all 40 rows, halo included (re-fetched: set_cfg / set_splits
-        reallocate the workspace)."""
-        return self.e().buffer(name + "+halo" if name in HALO_BUFS else name, BMAX)
+        """The stored buffer, every row of the engine, halo included (re-fetched: set_cfg /
+        set_splits reallocate the workspace)."""
+        return self.e().buffer(name + "+halo" if name in HALO_BUFS else name, self.rows)
 
     def gview(self, i):
         return param_views(self.grads, CANON_OFFSETS)[i]
@@ -84,6 +99,20 @@ def ctx():
     return Ctx(R.make_params(11))
 
 
+ROWS_BIG = 136
+# 128: a whole number of 16-, 32-, 64- and 128-row tiles (no partial tile, NB = 128); 129: one row
+# more than each (a full interior tile followed by a partial one; NB = 129 gives ragged K tiles in
+# every weight gradient)
+BATCHES_BIG = (128, 129)
+
+
+@pytest.fixture(scope="module")
+def ctx136():
+    """A 136-row engine on the same integer parameters: the fc ops have M = batch, so only past
+    128 rows is every row tile (32, 64 and 128 rows) filled and followed by another one."""
+    return Ctx(R.make_params(11), rows=ROWS_BIG)
+
+
 @pytest.fixture(scope="module")
 def rctx():
     """The same engine on real-valued, glorot-sized parameters with noisy biases."""
@@ -96,11 +125,7 @@ def rctx():
 
 
 # ---- exact: default config ------------------------------------------------------------------------
-@pytest.mark.parametrize("direct", [True, False])
-@pytest.mark.parametrize("B", BATCHES)
-def test_ops_exact_default_config(ctx, B, direct):
-    """All 17 ops through run_op(train=True) on the default config, the direct conv1 kernels on
-    and off."""
+def default_config_cases(ctx, B, direct):
     e = ctx.e()
     prev = e.conv1_direct(), e.conv1_wgrad_direct()
     fails = []
@@ -112,6 +137,23 @@ def test_ops_exact_default_config(ctx, B, direct):
     finally:
         e.set_conv1_direct(prev[0])
         e.set_conv1_wgrad_direct(prev[1])
+    return fails
+
+
+@pytest.mark.parametrize("direct", [True, False])
+@pytest.mark.parametrize("B", BATCHES)
+def test_ops_exact_default_config(ctx, B, direct):
+    """All 17 ops through run_op(train=True) on the default config, the direct conv1 kernels on
+    and off."""
+    fails = default_config_cases(ctx, B, direct)
+    assert not fails, "\n".join(fails)
+
+
+@pytest.mark.parametrize("direct", [True, False])
+@pytest.mark.parametrize("B", BATCHES_BIG)
+def test_ops_exact_default_config_past_128_rows(ctx136, B, direct):
+    """The same on the 136-row engine at B = 128 and 129."""
+    fails = default_config_cases(ctx136, B, direct)
     assert not fails, "\n".join(fails)
 
 
@@ -121,12 +163,7 @@ TILE_CFGS = [(c, None) for c in range(9)] + [(13, w) for w in (4, 8, 16)] + [(14
             [(15, w) for w in (4, 8, 16)]
 
 
-@pytest.mark.parametrize("cfg,waves", TILE_CFGS)
-@pytest.mark.parametrize("B", [5, 33])
-def test_ops_exact_tile_configs(ctx, B, cfg, waves):
-    """Every op on tile config `cfg` (ops without an instantiation of it fall back to the
-    one-wave 32x32 tile with the same split factor), splits 1 / 3 / default, in-launch and
-    separate split-K reduce; conv1 on the GEMM path so that its configs run too."""
+def tile_config_cases(ctx, B, cfg, waves):
     e = ctx.e()
     eng = ctx.eng
     base = eng.get_cfg(), eng.get_splits(), eng.get_wide()
@@ -154,6 +191,25 @@ def test_ops_exact_tile_configs(ctx, B, cfg, waves):
         eng.set_cfg(base[0])
         eng.set_splits(base[1])
         eng.set_wide(base[2])
+    return fails
+
+
+@pytest.mark.parametrize("cfg,waves", TILE_CFGS)
+@pytest.mark.parametrize("B", [5, 33])
+def test_ops_exact_tile_configs(ctx, B, cfg, waves):
+    """Every op on tile config `cfg` (ops without an instantiation of it fall back to the
+    one-wave 32x32 tile with the same split factor), splits 1 / 3 / default, in-launch and
+    separate split-K reduce; conv1 on the GEMM path so that its configs run too."""
+    fails = tile_config_cases(ctx, B, cfg, waves)
+    assert not fails, "\n".join(fails[:40])
+
+
+@pytest.mark.parametrize("cfg,waves", TILE_CFGS)
+def test_ops_exact_tile_configs_129_rows(ctx136, cfg, waves):
+    """The same sweep (every config, splits 1 / 3 / default, both reduce modes) at B = 129 on the
+    136-row engine: the 64-row tiles of configs 0, 2, 6, 7 are filled twice and the 128-row tile
+    of config 1 once, each followed by a one-row tile."""
+    fails = tile_config_cases(ctx136, 129, cfg, waves)
     assert not fails, "\n".join(fails[:40])
 
 
@@ -185,11 +241,7 @@ def segment_case(ctx, s, B):
     return ctx.cases[key]
 
 
-@pytest.mark.parametrize("dual", [True, False])
-@pytest.mark.parametrize("B", BATCHES)
-def test_backward_segments_exact(ctx, B, dual):
-    """backward_segment(1..3): the dual launches, run_dual_then with the direct conv1 weight
-    gradient and conv2's reduce inside it; then the same back to back (set_dual(False))."""
+def backward_segment_cases(ctx, B, dual):
     fails = []
     ctx.eng.set_dual(dual)
     try:
@@ -201,6 +253,23 @@ def test_backward_segments_exact(ctx, B, dual):
             fails += check(ctx, B, snap, ref, f"segment {s} B={B} dual={dual}")
     finally:
         ctx.eng.set_dual(True)
+    return fails
+
+
+@pytest.mark.parametrize("dual", [True, False])
+@pytest.mark.parametrize("B", BATCHES)
+def test_backward_segments_exact(ctx, B, dual):
+    """backward_segment(1..3): the dual launches, run_dual_then with the direct conv1 weight
+    gradient and conv2's reduce inside it; then the same back to back (set_dual(False))."""
+    fails = backward_segment_cases(ctx, B, dual)
+    assert not fails, "\n".join(fails)
+
+
+@pytest.mark.parametrize("dual", [True, False])
+@pytest.mark.parametrize("B", BATCHES_BIG)
+def test_backward_segments_exact_past_128_rows(ctx136, B, dual):
+    """The same on the 136-row engine at B = 128 and 129."""
+    fails = backward_segment_cases(ctx136, B, dual)
     assert not fails, "\n".join(fails)
 
 
@@ -235,6 +304,31 @@ def test_eval_forward_exact(ctx, B):
         fails += run_case(ctx, 0, B, f"eval conv1_direct={not prev}", train=False)
     finally:
         e.set_conv1_direct(prev)
+    assert not fails, "\n".join(fails)
+
+
+def test_eval_forward_exact_129_rows(ctx136):
+    """The eval forward cells of test_eval_forward_exact at B = 129 on the 136-row engine, then
+    fc1 and fc2 (run_op(train=False), M = 129) on each of the tile configs 0-8 as eval config."""
+    c = ctx136
+    e = c.e()
+    B = 129
+    fails = eval_cases(c, B, "rows=136")
+    prev = e.conv1_direct()
+    base = list(e.get_eval_cfg())
+    try:
+        e.set_conv1_direct(not prev)
+        fails += run_case(c, 0, B, f"eval conv1_direct={not prev}", train=False)
+        e.set_conv1_direct(prev)
+        for cfg in range(9):
+            ec = list(base)
+            ec[4] = ec[5] = cfg
+            e.set_eval_cfg(ec)
+            for op in (4, 5):
+                fails += run_case(c, op, B, f"rows=136 eval_cfg={cfg}", train=False)
+    finally:
+        e.set_conv1_direct(prev)
+        e.set_eval_cfg(base)
     assert not fails, "\n".join(fails)
 
 
@@ -359,7 +453,20 @@ def test_head_matches_reference(B, keep, kernel):
     B, keep and labels, the same for both kernel pairs: loss 1.39, dlog 0.35, dpre2fc 1.33,
     fc3 dW 0.63, db 0.35.
     """
-    c = Ctx(make_real_params())
+    fails = head_cases(Ctx(make_real_params()), B, keep, kernel)
+    assert not fails, "\n".join(fails)
+
+
+@pytest.mark.parametrize("kernel", ["fused", "fwd_bwd"])
+def test_head_matches_reference_129_rows(kernel):
+    """backward_segment(0) by the same rule at B = 129 and keep 0.5 on a 136-row engine:
+    head_fused's row tiles (bx = row >> 5) past the fourth, and the fc backward of the segment
+    at M = 129."""
+    fails = head_cases(Ctx(make_real_params(), rows=ROWS_BIG), 129, 0.5, kernel)
+    assert not fails, "\n".join(fails)
+
+
+def head_cases(c, B, keep, kernel):
     gen = torch.Generator().manual_seed(100 + B)
     if B > 1:
         h2, labels, extreme = head_inputs(c.P, B, gen, range(0, B, 3))
@@ -413,7 +520,7 @@ def test_head_matches_reference(B, keep, kernel):
                     fails.append(f"{n} rows >= {B} changed")
     finally:
         c.eng.set_concurrent(False)
-    assert not fails, "\n".join(fails)
+    return fails
 
 
 def test_slab_sized_for_every_smaller_batch():
@@ -427,7 +534,8 @@ def test_slab_sized_for_every_smaller_batch():
     params = torch.zeros(TOTAL_NUMEL, device=DEV)
     grads = torch.zeros_like(params)
     size = {}
-    for b in (33, BMAX):
-        eng = HipEngine(params, grads, CANON_OFFSETS, batch=b, graph=False, eval_chunk=BMAX)
-        size[b] = eng.eng.workspace_bytes()
-    assert size[BMAX] >= size[33]
+    for small, big in ((33, BMAX), (129, ROWS_BIG)):
+        for b in (small, big):
+            eng = HipEngine(params, grads, CANON_OFFSETS, batch=b, graph=False, eval_chunk=big)
+            size[b] = eng.eng.workspace_bytes()
+        assert size[big] >= size[small]

@@ -10,7 +10,8 @@ from ddl_amd.models.layout import CANON_OFFSETS, TOTAL_NUMEL
 from ddl_amd.models.mnist_cnn import (torch_forward, xent_loss, dropout_apply, init_params_,
                                       param_views)
 
-BATCHES = (1, 5, 33)   # the batches of tests/test_op_oracle_gpu.py
+BATCHES = (1, 5, 33)   # the batches of tests/test_op_oracle_gpu.py on its 40-row engine
+BATCHES_BIG = (128, 129)   # and on its 136-row engine
 
 
 def relerr(a, b):
@@ -111,7 +112,7 @@ def test_exactness_condition():
     P = R.make_params(1)
     assert all(float(p.abs().max()) <= R.INT_AMAX and torch.equal(p, p.round()) for p in P)
     assert all(bool((p != 0).all()) for p in P[1::2])   # non-zero biases
-    for B in BATCHES:
+    for B in BATCHES + BATCHES_BIG:
         for op in range(R.OP_COUNT):
             k = R.k_terms(op, B)
             assert k * R.INT_AMAX ** 2 < 2 ** 24, (R.OP_NAMES[op], B)
@@ -121,9 +122,19 @@ def test_exactness_condition():
                     assert float(v.abs().max()) <= R.INT_AMAX and torch.equal(v, v.round()), name
                     assert 0.3 < float((v == 0).float().mean()) < 0.75, name   # sparse
                     assert float(v.sum()) != 0, name
-    assert worst == (25872, ("conv1_wgrad", 33))
+        if B == BATCHES[-1]:
+            assert worst == (25872, ("conv1_wgrad", 33))
+    assert worst == (129 * 784, ("conv1_wgrad", 129))
     # dropout and its backward scale by 1 / keep = 2: still exact
     assert 2 * 1025 * R.INT_AMAX ** 2 < 2 ** 24
+    # the data itself, at the largest batch: the abs-sum of every weight-gradient element (an
+    # upper bound of each of its partial sums in any order) is an fp32 integer with room to spare
+    P64 = [p.double() for p in R.make_params(11)]
+    for op in (7, 9, 11, 13, 15, 16):
+        asum = R.abs_sum(op, P64, R.make_inputs(op, BATCHES_BIG[-1], 1), 0.5)
+        top = max(float(v.max()) for v in asum.values())
+        print(f"{R.OP_NAMES[op]} B={BATCHES_BIG[-1]}: largest abs-sum {top:.0f}")
+        assert top < 2 ** 20, R.OP_NAMES[op]
 
 
 def operands(op, P, buf):
