@@ -271,6 +271,14 @@ class PyEngine {
   void flush_update_tail(int64_t kind, at::Tensor w, at::Tensor g, c10::optional<at::Tensor> m,
                          c10::optional<at::Tensor> v, double step, double b1, double b2,
                          double eps, double mu, double scale, double decay, bool nesterov) {
+    queue_update_tail(kind, w, g, m, v, step, b1, b2, eps, mu, scale, decay, nesterov);
+    e_.flush_tail(cur_stream());
+  }
+  // the same one-piece tail left pending: the next launch that carries a tail takes it, or the
+  // next flush_tail launches it (tests; the tensors must outlive that launch)
+  void queue_update_tail(int64_t kind, at::Tensor w, at::Tensor g, c10::optional<at::Tensor> m,
+                         c10::optional<at::Tensor> v, double step, double b1, double b2,
+                         double eps, double mu, double scale, double decay, bool nesterov) {
     const FlatUpdate u(kind, w, g, m, v, b1, b2, eps, mu, scale, decay, nesterov);
     e_.flush_tail(cur_stream());
     ddl::UpdPiece q;
@@ -280,7 +288,15 @@ class PyEngine {
     e_.tail.rule = u.rule;
     e_.tail.add_piece(q);
     e_.tail.finish();
-    e_.flush_tail(cur_stream());
+  }
+  // host counters of the dispatch branches (kernels/api.h enum Branch), by name in enum order
+  py::dict dispatch_hits() const {
+    py::dict d;
+    for (int b = 0; b < ddl::BR_COUNT; ++b) d[ddl::Engine::branch_name(b)] = e_.branch_hits[b];
+    return d;
+  }
+  void reset_dispatch_hits() {
+    for (int& h : e_.branch_hits) h = 0;
   }
   void set_wide_thr(int64_t t) {
     e_.wide_thr = (int)std::max<int64_t>(1, t);
@@ -1074,6 +1090,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("g"), py::arg("m"), py::arg("v"), py::arg("step"), py::arg("b1"), py::arg("b2"),
            py::arg("eps"), py::arg("mu"), py::arg("scale"), py::arg("decay") = 0.0,
            py::arg("nesterov") = false)
+      .def("queue_update_tail", &PyEngine::queue_update_tail, py::arg("kind"), py::arg("w"),
+           py::arg("g"), py::arg("m"), py::arg("v"), py::arg("step"), py::arg("b1"), py::arg("b2"),
+           py::arg("eps"), py::arg("mu"), py::arg("scale"), py::arg("decay") = 0.0,
+           py::arg("nesterov") = false)
+      .def("dispatch_hits", &PyEngine::dispatch_hits)
+      .def("reset_dispatch_hits", &PyEngine::reset_dispatch_hits)
+      .def("set_fc_wgrad_defer", [](PyEngine& e, bool on) { e.raw()->fc_wgrad_defer = on; })
+      .def("fc_wgrad_defer", [](PyEngine& e) { return e.raw()->fc_wgrad_defer; })
       .def("set_conv1_direct", [](PyEngine& e, bool on) { e.raw()->conv1_direct = on; })
       .def("conv1_direct", [](PyEngine& e) { return e.raw()->conv1_direct; })
       .def("set_conv1_wgrad_direct", [](PyEngine& e, bool on) { e.raw()->conv1_wgrad_direct = on; })

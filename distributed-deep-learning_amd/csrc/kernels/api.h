@@ -184,6 +184,33 @@ constexpr int CFG_KW16 = 15;
 // (configs 16-20 — one-wave multi-fragment LDS-DMA tiles and the 32x32 ring tiles — were
 // measured in round 5, never won a launch and were removed: docs/DESIGN.md)
 
+// The run-time choices of a backward segment's launches (engine_impl.h, engine.hip), counted on
+// the host where each commits to its launches (Engine::branch_hits; tests prove with them that a
+// schedule reached the branch it was written for: configs fall back silently).  Names:
+// Engine::branch_name.
+enum Branch {
+  // an fc pair (data + weight gradient of fc2 / fc1): the packed launch with the weight gradient
+  // left to the conv4 dual launch, the packed launch that keeps it, the one-wave dual launch,
+  // back to back
+  BR_FC_PACK_DEFERRED = 0, BR_FC_PACK_KEPT, BR_FC_DUAL, BR_FC_BACK_TO_BACK,
+  // conv4's pair: the dual launch with the deferred fc weight gradients (FcWgradAux) or with the
+  // optimizer tail alone (TailAux); back to back with fc weight gradients left to flush_fc_wgrad,
+  // or with none pending
+  BR_CONV4_DUAL_FC_WGRAD, BR_CONV4_DUAL_TAIL, BR_CONV4_BACK_TO_BACK_FLUSH, BR_CONV4_BACK_TO_BACK,
+  BR_CONV3_DUAL, BR_CONV3_BACK_TO_BACK,
+  // conv2's pair inside the unfused sequence of segment 3
+  BR_CONV2_DUAL, BR_CONV2_BACK_TO_BACK,
+  // segment 3 fused (dual_then_b): conv1's direct kernel with conv2's reduce riding in it or with
+  // none pending; the reduce fused with conv1's GEMM (launch_reduce_with_gemm) or its refusal
+  // (launch_reduce, then run_op)
+  BR_SEG3_DIRECT_REDUCE, BR_SEG3_DIRECT, BR_SEG3_REDUCE_GEMM, BR_SEG3_REDUCE_REFUSED,
+  BR_SEG3_UNFUSED,            // run_dual_inst + run_op
+  BR_TAIL_STANDALONE,         // flush_tail issued update launches of its own
+  BR_TAIL_CONSUMED,           // a launch took the pending tail (dual, pack, FcWgradAux)
+  BR_CONCURRENT,              // a segment in the two-stream mode
+  BR_COUNT
+};
+
 struct Engine {
   const float* P[14] = {};   // parameter tensors v0..v13 (any flat layout)
   float* G[14] = {};         // gradient tensors v0..v13
@@ -231,6 +258,17 @@ struct Engine {
   // stand-alone optimizer launches flush_tail() has issued for update tails no launch took
   // (host counter, diagnostic: SyncRunner::update_launches)
   int update_launches = 0;
+  // host counters of the dispatch branches taken since the last reset (enum Branch)
+  int branch_hits[BR_COUNT] = {};
+  static const char* branch_name(int b);
+  void hit(Branch b) { ++branch_hits[b]; }
+  // the pending tail, handed to the launch that carries it
+  UpdTail take_tail() {
+    const UpdTail t = tail;
+    if (t.nblocks > 0) hit(BR_TAIL_CONSUMED);
+    tail = UpdTail();
+    return t;
+  }
   // eval forward: conv2 on the tap-skipping K map (DDL_EVAL_KMAP2=0: the image-major GEMM)
   bool eval_kmap2 = [] {
     const char* e = getenv("DDL_EVAL_KMAP2");

@@ -238,12 +238,25 @@ void Engine::flush_tail(hipStream_t st) {
     tail = UpdTail();
     return;
   }
+  int launched = 0;
   for (int i = 0; i < tail.npieces; ++i) {
     const UpdPiece& p = tail.p[i];
     launch_update(tail.rule, p.step, p.span(0), p.g, p.n, st);
-    update_launches += p.n > 0;
+    launched += p.n > 0;
   }
+  update_launches += launched;
+  if (launched) hit(BR_TAIL_STANDALONE);
   tail = UpdTail();
+}
+
+const char* Engine::branch_name(int b) {
+  static const char* const names[BR_COUNT] = {
+      "fc_pack_deferred", "fc_pack_kept", "fc_dual", "fc_back_to_back",
+      "conv4_dual_fc_wgrad", "conv4_dual_tail", "conv4_back_to_back_flush", "conv4_back_to_back",
+      "conv3_dual", "conv3_back_to_back", "conv2_dual", "conv2_back_to_back",
+      "seg3_direct_reduce", "seg3_direct", "seg3_reduce_gemm", "seg3_reduce_refused",
+      "seg3_unfused", "tail_standalone", "tail_consumed", "concurrent"};
+  return b >= 0 && b < BR_COUNT ? names[b] : "";
 }
 
 void Engine::flush_fc_wgrad(const float* x, int B, const uint32_t* seed, hipStream_t st) {
@@ -292,6 +305,7 @@ void Engine::wgrad(int op, const float* x, int B, const uint32_t* seed, hipStrea
 void Engine::backward_segment(int s, const float* x, const int64_t* labels, int B,
                               const uint32_t* seed, hipStream_t st) {
   if (concurrent && side) {  // weight gradients on the side stream (fork/join per segment)
+    hit(BR_CONCURRENT);
     flush_tail(st);
     flush_fc2(seed, B, st);
     switch (s) {

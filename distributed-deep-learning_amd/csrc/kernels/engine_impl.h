@@ -217,8 +217,7 @@ inline FcWgradAux fc_wgrad_aux(Engine& e, int B, const float* x, const uint32_t*
     a.n1 = a.gx1 * ((a.p1.N + 31) / 32);
   }
   e.fc_wgrad_pending = 0;
-  a.t = e.tail;
-  e.tail = UpdTail();
+  a.t = e.take_tail();
   a.first_ = 0;  // (tiles, then the tail, after the GEMM blocks)
   a.nblk = a.n2 + a.n1 + a.t.nblocks;
   return a;
@@ -242,6 +241,11 @@ inline HeadWgradAux head_aux(Engine& e, int B) {
 template <int OA, int OB>
 inline void run_back_to_back(Engine& e, const float* x, int B, const uint32_t* seed,
                              hipStream_t st) {
+  if constexpr (OA == OP_FC2_DGRAD || OA == OP_FC1_DGRAD) e.hit(BR_FC_BACK_TO_BACK);
+  else if constexpr (OA == OP_CONV4_DGRAD)  // (backward_segment flushes what is pending)
+    e.hit(e.fc_wgrad_pending ? BR_CONV4_BACK_TO_BACK_FLUSH : BR_CONV4_BACK_TO_BACK);
+  else if constexpr (OA == OP_CONV3_DGRAD) e.hit(BR_CONV3_BACK_TO_BACK);
+  else e.hit(BR_CONV2_BACK_TO_BACK);
   e.flush_tail(st);
   if constexpr (OA == OP_FC2_DGRAD) e.flush_head_wgrad(B, st);
   run_op_inst<OA>(e, x, B, seed, true, st, 0);
@@ -258,18 +262,21 @@ inline void dual_b(Engine& e, const PA& pa, const PB& pb, int B, hipStream_t st)
   // the fc2 dual carries fc3's weight gradient; the conv4 dual the deferred fc weight
   // gradients (if any) and the pending optimizer tail; the others the tail
   if constexpr (OA == OP_FC2_DGRAD) {
+    e.hit(BR_FC_DUAL);
     e.flush_tail(st);
     go(head_aux(e, B));
   } else if constexpr (OA == OP_CONV4_DGRAD) {
     if (e.fc_wgrad_pending) {
+      e.hit(BR_CONV4_DUAL_FC_WGRAD);
       go(fc_wgrad_aux(e, B, nullptr, nullptr));
     } else {
-      go(TailAux(e.tail));
-      e.tail = UpdTail();
+      e.hit(BR_CONV4_DUAL_TAIL);
+      go(TailAux(e.take_tail()));
     }
   } else {
-    go(TailAux(e.tail));
-    e.tail = UpdTail();
+    e.hit(OA == OP_FC1_DGRAD ? BR_FC_DUAL
+                             : OA == OP_CONV3_DGRAD ? BR_CONV3_DUAL : BR_CONV2_DUAL);
+    go(TailAux(e.take_tail()));
   }
 }
 
@@ -291,12 +298,12 @@ void run_dual_inst(Engine& e, const float* x, int B, const uint32_t* seed, hipSt
         e.fc_wgrad_pending |= OA == OP_FC2_DGRAD ? 1 : 2;
         pb.M = 0;
       }
+      e.hit(e.fc_wgrad_defer ? BR_FC_PACK_DEFERRED : BR_FC_PACK_KEPT);
       if constexpr (OA == OP_FC2_DGRAD) {
         e.flush_tail(st);
         launch_gemm_pack(pa, e.splits[OA], pb, head_aux(e, B), st);
       } else {
-        launch_gemm_pack(pa, e.splits[OA], pb, TailAux(e.tail), st);
-        e.tail = UpdTail();
+        launch_gemm_pack(pa, e.splits[OA], pb, TailAux(e.take_tail()), st);
       }
       return;
     }
@@ -446,9 +453,8 @@ void dual_then_b(Engine& e, const float* x, int B, const uint32_t* seed, hipStre
   using CN = TileCfg<TILE_3>;
   SubGrid gb;
   launch_gemm_dual<CA, PA, CB, PB>(pa, e.splits[OA], e.scratch[0], e.wide[OA], pb,
-                                   e.splits[OB], e.scratch[1], e.wide[OB], st, TailAux(e.tail),
-                                   &gb, e.dual_order(OA));
-  e.tail = UpdTail();
+                                   e.splits[OB], e.scratch[1], e.wide[OB], st,
+                                   TailAux(e.take_tail()), &gb, e.dual_order(OA));
   constexpr bool kFinal = ON == OP_CONV1_WGRAD;
   if constexpr (kFinal) {
     // conv1's weight gradient on the direct kernel (conv1.h), sharing its launch with OB's
@@ -457,6 +463,7 @@ void dual_then_b(Engine& e, const float* x, int B, const uint32_t* seed, hipStre
     const bool direct =
         e.conv1_wgrad_direct && conv1_wgrad_direct_ok(B, e.slab_floats, e.scratch[0].max_tiles);
     if (direct) {
+      e.hit(gb.mode == 2 ? BR_SEG3_DIRECT_REDUCE : BR_SEG3_DIRECT);
       float* part = static_cast<float*>(e.scratch[0].slab);
       // the last segment's update (W = 1 tail path) inside this launch: conv2's in its weight-
       // gradient reduce epilogue, conv1's in the final reduce level; no Adam launch follows
@@ -480,10 +487,12 @@ void dual_then_b(Engine& e, const float* x, int B, const uint32_t* seed, hipStre
   if (!launch_reduce_with_gemm<CB, PB, CN, PN>(pb, gb, pn, e.splits[ON], e.wide[ON],
                                                e.scratch[0], st,
                                                fin ? &gn : nullptr)) {
+    e.hit(BR_SEG3_REDUCE_REFUSED);
     launch_reduce<CB::BM, CB::BN, CB::BK, CB::WM, CB::WN, PB>(pb, gb, st);
     e.run_op(ON, x, B, seed, true, st, 0);
     return;
   }
+  e.hit(BR_SEG3_REDUCE_GEMM);
   if constexpr (kFinal) {
     if (fin) {
       // conv1's weight-gradient reduce applies conv1's update in its epilogue and carries the
@@ -506,6 +515,7 @@ void run_dual_then_inst(Engine& e, const float* x, int B, const uint32_t* seed, 
   const int ca = e.cfg[OA], cb = e.cfg[OB];
   if (!e.dual || (ca != 3 && ca != CFG_MF16) || (cb != 3 && cb != 5 && cb != CFG_MF16) ||
       e.cfg[ON] != 3) {
+    e.hit(BR_SEG3_UNFUSED);
     run_dual_inst<OA, OB>(e, x, B, seed, st);
     e.run_op(ON, x, B, seed, true, st, 0);
     return;
@@ -518,6 +528,7 @@ void run_dual_then_inst(Engine& e, const float* x, int B, const uint32_t* seed, 
       if constexpr (A != 5 && dual_pair_ok(A, Bc)) {
         dual_then_b<OA, OB, ON, typename CfgOf<A>::T, typename CfgOf<Bc>::T>(e, x, B, seed, st);
       } else {
+        e.hit(BR_SEG3_UNFUSED);
         run_dual_inst<OA, OB>(e, x, B, seed, st);
         e.run_op(ON, x, B, seed, true, st, 0);
       }

@@ -239,21 +239,27 @@ def final_split_conv12_ok(pieces, offsets):
 
 
 def expected_update_launches(seg_pieces, merged, offsets, use_tail=True, final_in_reduce=True,
-                             dual=True, conv1_direct=True, per_segment=False):
+                             dual=True, conv1_direct=True, per_segment=False,
+                             pair_takes=(True, True, True), conv2_reduce_separate=True):
     """Stand-alone optimizer launches of one W = 1 step (update_launches() of either runner), by
     reading SyncRunner::step, AsyncRunner::step_inline and run_riding_backward (runner.hip).  Every
     plan buffer keeps tensors and PS chunks on 64-element boundaries, so the alignment and length
     conditions of tail_ok always hold here; what decides is the piece count.  per_segment: the
     in-line runner's policy, a segment with more than TAIL_PIECES pieces is launched piece by
     piece and the others still ride; otherwise one such segment sends every update after the
-    backward (SyncRunner)."""
+    backward (SyncRunner).  pair_takes: whether the launches of conv4's / conv3's / conv2's pair
+    carry a tail (a pair with an op on a config without a dual launch runs back to back and
+    flushes it: engine_impl.h run_dual_inst); conv2_reduce_separate: conv2's weight gradient leaves
+    a separate reduce (mode 2) for conv1's launch, whose epilogue is what applies the last
+    segment's update (dual_then_b)."""
     rides = [len(sp) <= TAIL_PIECES for sp in seg_pieces]
     if not per_segment and not (use_tail and all(rides)):
         return len(merged)           # the coalesced launches after the backward
     # (without dual launches run_back_to_back flushes the pending tail, a launch per piece)
-    n = sum(len(sp) for sp, r in zip(seg_pieces[:-1], rides) if not (r and dual))
+    n = sum(len(sp) for sp, r, takes in zip(seg_pieces[:-1], rides, pair_takes)
+            if not (r and dual and takes))
     last = seg_pieces[-1]
-    taken = rides[-1] and final_in_reduce and dual
+    taken = rides[-1] and final_in_reduce and dual and pair_takes[-1] and conv2_reduce_separate
     if conv1_direct:                 # (else final_split + launch_reduce_tail: conv1's spans cut out)
         taken = taken and final_split_conv12_ok(last, offsets)
     return n + (0 if taken else len(last))

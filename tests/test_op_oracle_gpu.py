@@ -34,72 +34,20 @@ import torch
 import op_reference as R
 from ddl_amd.models.layout import CANON_OFFSETS, TOTAL_NUMEL
 from ddl_amd.models.mnist_cnn import init_params_, param_views
-from oracle_common import (BATCHES, BMAX, DEV, HALO_BUFS, HEAD_MARGIN, KEEP, SEED, bits, check,
-                           make_real_params, prepare)
+from oracle_common import (BATCHES, BMAX, DEV, HEAD_MARGIN, KEEP, ROWS_BIG, SEED, WIDE_INLAUNCH,
+                           WIDE_SEPARATE, Ctx, bits, check, head_inputs, make_real_params, prepare,
+                           run_case, segment_case)
 
 pytestmark = pytest.mark.gpu
 
-WIDE_INLAUNCH, WIDE_SEPARATE = 1 << 20, 1
 
-
-class Ctx:
-    """An engine of `rows` rows (40 by default) on the parameters `P` (CPU fp32 tensors), and a
-    cache of cases."""
-
-    def __init__(self, P, rows=BMAX):
-        from ddl_amd.models.hip_engine import HipEngine
-        self.P = P
-        self.rows = rows
-        self.P64 = [p.double() for p in P]
-        self.params = torch.zeros(TOTAL_NUMEL, device=DEV)
-        self.grads = torch.zeros_like(self.params)
-        self.offsets = CANON_OFFSETS
-        self.eng = HipEngine(self.params, self.grads, CANON_OFFSETS, batch=rows, graph=False,
-                             eval_chunk=rows, keep_prob=KEEP)
-        # in place: the engine holds pointers into the flat tensor
-        self.params.copy_(torch.cat([p.reshape(-1) for p in P]))
-        self.seed_t = torch.tensor([SEED], dtype=torch.int32, device=DEV)
-        self.labels = torch.zeros(rows, dtype=torch.int64, device=DEV)
-        self.cases = {}
-
-    def e(self):
-        return self.eng.eng
-
-    def whole(self, name):
-        """The stored buffer, every row of the engine, halo included (re-fetched: set_cfg /
-        set_splits reallocate the workspace)."""
-        return self.e().buffer(name + "+halo" if name in HALO_BUFS else name, self.rows)
-
-    def gview(self, i):
-        return param_views(self.grads, CANON_OFFSETS)[i]
-
-    def poison_grads(self):
-        self.grads.fill_(float("nan"))
-
-    def case(self, op, B, train=True, real=False):
-        """(inputs, fp64 reference outputs) of op at batch B, computed once: the reference is
-        exact, so every config shares it."""
-        key = (op, B, train, real)
-        if key not in self.cases:
-            inp = R.make_inputs(op, B, 1, real)
-            self.cases[key] = (inp, R.run_op(op, self.P64, inp, SEED, KEEP, train))
-        return self.cases[key]
-
-
-def run_case(ctx, op, B, tag, train=True):
-    inputs, ref = ctx.case(op, B, train)
-    x, snap = prepare(ctx, B, inputs)
-    ctx.e().run_op(op, x, ctx.seed_t, train)
-    torch.cuda.synchronize()
-    return check(ctx, B, snap, ref, f"{R.OP_NAMES[op]} B={B} {tag}")
-
-
+# (Ctx, run_case, segment_case and head_inputs: tests/oracle_common.py, shared with
+# tests/test_dispatch_oracle_gpu.py)
 @pytest.fixture(scope="module")
 def ctx():
     return Ctx(R.make_params(11))
 
 
-ROWS_BIG = 136
 # 128: a whole number of 16-, 32-, 64- and 128-row tiles (no partial tile, NB = 128); 129: one row
 # more than each (a full interior tile followed by a partial one; NB = 129 gives ragged K tiles in
 # every weight gradient)
@@ -214,33 +162,6 @@ def test_ops_exact_tile_configs_129_rows(ctx136, cfg, waves):
 
 
 # ---- exact: the default launches of backward_segment --------------------------------------------------
-SEGMENT_OPS = {1: (10, 11), 2: (12, 13), 3: (14, 15, 16)}
-
-
-def segment_case(ctx, s, B):
-    """Hand-written integer inputs of segment s and the references of its ops; conv1's weight
-    gradient (segment 3) reads the d1 that conv2's data gradient writes."""
-    key = ("seg", s, B)
-    if key not in ctx.cases:
-        inputs, ref = {}, {}
-        for op in SEGMENT_OPS[s]:
-            if op == 16:
-                inp = {"x": R.make_inputs(16, B, 1)["x"], "d1": ref["d1"].to(torch.float32)}
-                # exactness of the chained op: its abs-sums (an upper bound of every partial sum)
-                # are fp32 integers
-                asum = R.abs_sum(16, ctx.P64, inp, KEEP)
-                assert max(float(v.max()) for v in asum.values()) < 2 ** 24
-                inputs["x"] = inp["x"]
-            else:
-                inp = R.make_inputs(op, B, 1)
-                for k, v in inp.items():
-                    inputs.setdefault(k, v)
-                inp = {k: inputs[k] for k in inp}
-            ref.update(R.run_op(op, ctx.P64, inp, SEED, KEEP, True))
-        ctx.cases[key] = (inputs, ref)
-    return ctx.cases[key]
-
-
 def backward_segment_cases(ctx, B, dual):
     fails = []
     ctx.eng.set_dual(dual)
@@ -415,28 +336,6 @@ def test_ops_real_valued_precision(rctx, op):
 
 
 # ---- classifier head -----------------------------------------------------------------------------------
-def head_inputs(P, B, gen, extreme_rows):
-    """h2 rows: ordinary ones, and the rows `extreme_rows` along W3[:, a] - W3[:, b] scaled so
-    that their largest |logit| is about 60, labelled with their largest or smallest logit in
-    turn."""
-    w3, b3 = P[12].double(), P[13].double()
-    h2 = (torch.rand(B, 512, generator=gen) * 1.5 - 0.5)
-    labels = torch.randperm(max(B, 10), generator=gen)[:B] % 10
-    extreme = torch.zeros(B, dtype=torch.bool)
-    for i, r in enumerate(extreme_rows):
-        a, b = r % 10, (r + 3) % 10
-        d = w3[:, a] - w3[:, b]
-        h2[r] = (d * (60.0 / float((d @ w3).abs().max()))).float()
-        extreme[r] = True
-        lg = h2[r].double() @ w3 + b3
-        assert 50 < float(lg.abs().max()) < 70
-        if i % 3 == 0:
-            labels[r] = int(lg.argmax())
-        elif i % 3 == 1:
-            labels[r] = int(lg.argmin())
-    return h2, labels, extreme
-
-
 @pytest.mark.parametrize("kernel", ["fused", "fwd_bwd"])
 @pytest.mark.parametrize("keep", [0.5, 1.0])
 @pytest.mark.parametrize("B", [1, 33])

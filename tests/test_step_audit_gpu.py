@@ -65,6 +65,9 @@ all 128 audited buffers; inside the ceiling of a tie (flat, step 0, B = 1 / 5 / 
 c2 9 / 52 / 427, c3 15 / 65 / 448, c4 15 / 89 / 539.  Update: |w - closed form| <= 3.0e-8, m
 within 8.8e-8, v within 9.6e-8.  update_launches() equalled LAUNCHES in every cell: 0 everywhere
 except greedy-ps3 3, flat-ps3 3, flat-ps7 28, flat-last-alone 1, flat-no-tail 1, flat-no-dual 4.
+(Three cells added later, off the default schedule: flat-conv4-b2b 1, flat-conv2-inlaunch 1,
+flat-fc-dual 0, as read from the code and as the GPU gave them; 0.23-0.36 s each, the file's 59
+tests 8.9 s.)
 """
 import time
 
@@ -114,6 +117,23 @@ def _fc2_split(tr):
     e.set_splits(sp)
 
 
+def _schedule(cfg=None, wide=None):
+    """Tile configs / wide thresholds by op (csrc/kernels/api.h enum Op) over the defaults."""
+    def setup(tr):
+        e = tr.engine.eng
+        if cfg:
+            cf = e.get_cfg()
+            for op, c in cfg.items():
+                cf[op] = c
+            e.set_cfg(cf)
+        if wide:
+            wd = e.get_wide()
+            for op, w in wide.items():
+                wd[op] = w
+            e.set_wide(wd)
+    return setup
+
+
 def cell(shard, batches=BATCHES, setup=None, variant="default", flags=None, **kw):
     return dict(shard=shard, **kw), setup, batches, variant, flags or {}
 
@@ -149,6 +169,14 @@ CELLS = {
     "flat-tail-1-128": cell("flat", (5,), _runner(set_tail_cfg=(1, 128))),
     "flat-tail-1-1024": cell("flat", (5,), _runner(set_tail_cfg=(1, 1024))),
     "flat-fc2-split": cell("flat", BATCHES, _fc2_split, "fc2-split"),
+    # dispatch branches off the default schedule (tests/test_dispatch_oracle_gpu.py runs them
+    # segment by segment): conv4's data gradient (op 10) on config 0, conv2's weight gradient
+    # (op 15) reduced in its launch, the fc data gradients (ops 6, 8) on the one-wave 32x32 tile
+    "flat-conv4-b2b": cell("flat", (5,), _schedule(cfg={10: 0}), "conv4-b2b",
+                           flags=dict(pair_takes=(False, True, True))),
+    "flat-conv2-inlaunch": cell("flat", (5,), _schedule(wide={15: 1 << 20}), "conv2-inlaunch",
+                                flags=dict(conv2_reduce_separate=False)),
+    "flat-fc-dual": cell("flat", (5,), _schedule(cfg={6: 3, 8: 3}), "fc-dual"),
 }
 
 # runner.update_launches() of a step: the stand-alone optimizer launches.  Read off UpdatePlan
@@ -192,6 +220,16 @@ LAUNCHES = {
     "flat-tail-0-128": 0, "flat-tail-0-1024": 0, "flat-tail-1-128": 0, "flat-tail-1-1024": 0,
     # the head takes fc2's reduce; the updates ride as in "flat"
     "flat-fc2-split": 0,
+    # the conv4 pair runs back to back and its flush_tail launches segment 0's piece; the fc weight
+    # gradients go through flush_fc_wgrad; the other segments ride
+    "flat-conv4-b2b": 1,
+    # conv2's weight gradient is final when its dual launch ends (gb.mode == 1): conv1's direct
+    # kernel has no reduce epilogue to apply conv2's update in, so dual_then_b leaves final_upd and
+    # the runner launches segment 3's piece
+    "flat-conv2-inlaunch": 1,
+    # no tail is pending at segment 0; the fc pairs run as one-wave dual launches that keep their
+    # weight gradients, and the conv4 dual carries segment 0's piece as a plain TailAux
+    "flat-fc-dual": 0,
 }
 assert LAUNCHES.keys() == CELLS.keys()
 
