@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "kernels/api.h"
+#include "kernels/fake_rccl.h"
 #include "kernels/stamps.h"
 #include "runtime/mailbox.h"
 
@@ -985,6 +986,80 @@ class PyRunner {
   PyPeer* peer_keep_ = nullptr;
 };
 
+// ---- the fake RCCL behind rccl_api.h's override seam (kernels/fake_rccl.hip; tests only) --------
+std::vector<at::Tensor>& fake_rccl_keep() {
+  static std::vector<at::Tensor> keep;  // (buffers the fake holds raw pointers into)
+  return keep;
+}
+std::vector<at::Tensor>& fake_rccl_step_keep() {
+  static std::vector<at::Tensor> keep;
+  return keep;
+}
+
+int64_t& fake_rccl_world() {
+  static int64_t w = 0;
+  return w;
+}
+
+void fake_rccl_install(int64_t world, int64_t rank, at::Tensor params, at::Tensor grads,
+                       std::vector<at::Tensor> shards, c10::optional<at::Tensor> seen) {
+  check_f32_cuda(params, "params");
+  check_f32_cuda(grads, "grads");
+  ddl::fake_rccl::Config c;
+  c.world = (int)world, c.rank = (int)rank;
+  c.params = {params.data_ptr<float>(), params.numel()};
+  c.grads = {grads.data_ptr<float>(), grads.numel()};
+  std::vector<at::Tensor> keep{params, grads};
+  for (auto& s : shards) {
+    check_f32_cuda(s, "shard");
+    c.shards.push_back({s.data_ptr<float>(), s.numel()});
+    keep.push_back(s);
+  }
+  if (seen.has_value()) {
+    check_f32_cuda(*seen, "seen");
+    TORCH_CHECK(seen->numel() == grads.numel(), "seen: the gradient buffer's length");
+    c.seen = seen->data_ptr<float>();
+    keep.push_back(*seen);
+  }
+  ddl::fake_rccl::install(c);
+  fake_rccl_world() = world;
+  fake_rccl_keep() = keep;
+  fake_rccl_step_keep().clear();
+}
+
+void fake_rccl_remove() {
+  ddl::fake_rccl::remove();
+  fake_rccl_keep().clear();
+  fake_rccl_step_keep().clear();
+}
+
+void fake_rccl_set_step(at::Tensor peer_grads, at::Tensor params_next) {
+  check_f32_cuda(peer_grads, "peer_grads");
+  check_f32_cuda(params_next, "params_next");
+  TORCH_CHECK(!fake_rccl_keep().empty(), "fake RCCL not installed");
+  const int64_t total = fake_rccl_keep()[0].numel();
+  TORCH_CHECK(peer_grads.dim() == 2 && peer_grads.size(0) == fake_rccl_world() &&
+                  peer_grads.size(1) == total && params_next.numel() == total,
+              "peer_grads [W, total] and params_next [total]");
+  ddl::fake_rccl::set_step(peer_grads.data_ptr<float>(), params_next.data_ptr<float>());
+  fake_rccl_step_keep() = {peer_grads, params_next};
+}
+
+int fake_rccl_code(const std::string& name, const std::vector<const char*>& names) {
+  for (size_t i = 0; i < names.size(); ++i)
+    if (name == names[i]) return (int)i;
+  TORCH_CHECK(false, "fake RCCL: unknown name '", name, "'");
+  return -1;
+}
+
+py::list fake_rccl_calls() {
+  py::list out;
+  for (const auto& c : ddl::fake_rccl::calls())
+    out.append(py::make_tuple(c.op, c.buf, c.off, c.count, c.root, c.stream, c.depth, c.rbuf,
+                              c.roff));
+  return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1255,4 +1330,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("size", &ddl::ShmMailbox::size)
       .def("capacity", &ddl::ShmMailbox::capacity)
       .def("unlink", &ddl::ShmMailbox::unlink);
+
+  // the fake RCCL of the rank tests (kernels/fake_rccl.hip): install / remove the override table
+  m.def("fake_rccl_install", &fake_rccl_install, py::arg("world"), py::arg("rank"),
+        py::arg("params"), py::arg("grads"), py::arg("shards"), py::arg("seen") = py::none(),
+        "Configure the fake RCCL and put its table into the RCCL seam (refused while a "
+        "SyncRunner holds a communicator)");
+  m.def("fake_rccl_remove", &fake_rccl_remove, "Take the fake RCCL's table out of the seam");
+  m.def("rccl_overridden", [] { return ddl::fake_rccl::overridden(); });
+  m.def("fake_rccl_set_step", &fake_rccl_set_step, py::arg("peer_grads"), py::arg("params_next"));
+  m.def("fake_rccl_set_peers", [](const std::string& n) {
+    ddl::fake_rccl::set_peers(fake_rccl_code(n, {"table", "pattern"}));
+  });
+  m.def("fake_rccl_set_fault", [](const std::string& n) {
+    ddl::fake_rccl::set_fault(fake_rccl_code(
+        n, {"none", "rs_next_chunk", "ag_skip", "reduce_drop_peer", "bcast_skip"}));
+  });
+  m.def("fake_rccl_clear", &ddl::fake_rccl::clear);
+  m.def("fake_rccl_calls", &fake_rccl_calls,
+        "(op, buffer, offset, count, root, stream, group depth, recv buffer, recv offset)");
+  m.def("fake_rccl_violations", &ddl::fake_rccl::violations);
+  m.def("fake_rccl_group_depth", &ddl::fake_rccl::group_depth);
 }

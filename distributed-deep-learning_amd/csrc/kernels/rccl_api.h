@@ -7,6 +7,7 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
+#include <atomic>
 #include <stdexcept>
 #include <string>
 
@@ -32,7 +33,29 @@ struct RcclApi {
   decltype(&ncclCommAbort) CommAbort = nullptr;
 };
 
+// The test seam: an override table that stands in for librccl (fake_rccl.hip is the one user).
+// One pointer, null in every real job; SyncRunner counts its live communicators so that a table
+// is never swapped under a communicator that the other table made.
+inline std::atomic<const RcclApi*>& rccl_override_slot() {
+  static std::atomic<const RcclApi*> slot{nullptr};
+  return slot;
+}
+inline std::atomic<int>& rccl_live_comms() {
+  static std::atomic<int> n{0};
+  return n;
+}
+inline bool rccl_overridden() {
+  return rccl_override_slot().load(std::memory_order_acquire) != nullptr;
+}
+// install (a table) or remove (nullptr); refused while a SyncRunner holds a communicator
+inline void set_rccl_override(const RcclApi* table) {
+  if (rccl_live_comms().load() > 0)
+    throw std::runtime_error("RCCL override: a SyncRunner still holds a communicator");
+  rccl_override_slot().store(table, std::memory_order_release);
+}
+
 inline const RcclApi& rccl() {
+  if (const RcclApi* o = rccl_override_slot().load(std::memory_order_acquire)) return *o;
   static RcclApi api = [] {
     RcclApi a;
     void* h = dlopen("librccl.so", RTLD_NOW | RTLD_NOLOAD);

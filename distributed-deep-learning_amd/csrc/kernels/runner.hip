@@ -182,7 +182,10 @@ SyncRunner::SyncRunner(Engine* eng, float* params, float* grads, int world, int 
 }
 
 SyncRunner::~SyncRunner() {
-  if (comm_) (void)rccl().CommDestroy(as_comm(comm_));
+  if (comm_) {
+    (void)rccl().CommDestroy(as_comm(comm_));
+    --rccl_live_comms();
+  }
   comm_ = nullptr;
   release();
 }
@@ -216,6 +219,8 @@ void SyncRunner::unique_id(char out[128]) {
 }
 
 std::string SyncRunner::probe() {
+  // (an override table is a test's stand-in, never a library a job may train on)
+  if (rccl_overridden()) return "an RCCL override table is installed";
   try {
     (void)rccl();
   } catch (const std::exception& e) {
@@ -231,6 +236,7 @@ void SyncRunner::init_comm(const char id_bytes[128], bool force) {
   ncclComm_t c;
   RCCL_CHECK(rccl().CommInitRank(&c, world_, id, rank_));
   comm_ = c;
+  ++rccl_live_comms();
 }
 
 void SyncRunner::set_units(const std::vector<RunnerUnit>& units) {
@@ -595,6 +601,7 @@ void SyncRunner::close() {
     HIP_CHECK(hipStreamSynchronize(cs_));
     (void)rccl().CommDestroy(as_comm(comm_));
     comm_ = nullptr;
+    --rccl_live_comms();
   }
   // and every stream / event / flag with it: a closed runner holds no hardware queue (the
   // one-card W = 4 rehearsal kept four processes' released runners' queues until GC)
@@ -605,6 +612,7 @@ void SyncRunner::abort() {
   if (!comm_) return;
   (void)rccl().CommAbort(as_comm(comm_));
   comm_ = nullptr;
+  --rccl_live_comms();
 }
 
 // Collective sanity check used before trusting the native path on a multi-GPU job: the RS
