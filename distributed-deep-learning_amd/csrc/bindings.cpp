@@ -226,36 +226,30 @@ class PyEngine {
     realloc();
   }
 
-  void set_cfg(std::vector<int64_t> c) {
+  // Tile configs of the training step or of the eval forward (no split-K, large batch chunks; no
+  // slab needed).  Accepted: a config the op has an instantiation of, or a special one, which
+  // falls back where the op has none (the defaults hold those): effective_cfg() tells
+  void set_cfgs(std::vector<int64_t> c, bool train) {
     TORCH_CHECK((int)c.size() == ddl::OP_COUNT, "expected ", (int)ddl::OP_COUNT, " tile configs");
-    for (int i = 0; i < ddl::OP_COUNT; ++i) {
-      TORCH_CHECK((c[i] >= 0 && c[i] < ddl::NUM_TILE_CFGS) || c[i] == ddl::CFG_KWAVE ||
-                      c[i] == ddl::CFG_MF16 || c[i] == ddl::CFG_KW16,
+    for (int i = 0; i < ddl::OP_COUNT; ++i)
+      TORCH_CHECK(c[i] >= 0 && c[i] <= ddl::CFG_KW16 && ddl::cfg_accepted(i, (int)c[i], train),
                   "tile config out of range");
-      e_.cfg[i] = (int)c[i];
-    }
-    realloc();
+    int* dst = train ? e_.sched.cfg : e_.sched.eval_cfg;
+    for (int i = 0; i < ddl::OP_COUNT; ++i) dst[i] = (int)c[i];
+    if (train) realloc();
   }
-  std::vector<int64_t> get_cfg() const {
-    return std::vector<int64_t>(e_.cfg, e_.cfg + ddl::OP_COUNT);
+  void set_cfg(std::vector<int64_t> c) { set_cfgs(c, true); }
+  void set_eval_cfg(std::vector<int64_t> c) { set_cfgs(c, false); }
+  std::vector<int64_t> get_cfg() const { return vec(e_.sched.cfg); }
+  std::vector<int64_t> get_eval_cfg() const { return vec(e_.sched.eval_cfg); }
+  // the configs that really run (kernels/schedule.h effective_cfg)
+  std::vector<int64_t> effective(bool train) const {
+    auto c = vec(train ? e_.sched.cfg : e_.sched.eval_cfg);
+    for (int i = 0; i < ddl::OP_COUNT; ++i) c[i] = ddl::effective_cfg(i, (int)c[i], train);
+    return c;
   }
-  // tile configs of the eval forward (no split-K, large batch chunks); no slab needed
-  void set_eval_cfg(std::vector<int64_t> c) {
-    TORCH_CHECK((int)c.size() == ddl::OP_COUNT, "expected ", (int)ddl::OP_COUNT, " tile configs");
-    for (int i = 0; i < ddl::OP_COUNT; ++i) {
-      // the eval-only large tiles exist for the conv2-4 forward ops only
-      const bool big = i == ddl::OP_CONV2_FWD || i == ddl::OP_CONV3_FWD || i == ddl::OP_CONV4_FWD;
-      // (CFG_KWAVE / CFG_MF16 / CFG_KW16 — the engine's own defaults hold the latter two, so
-      // get_eval_cfg's list can be set back; ops without an instantiation of one fall back to the
-      // one-wave 32x32 tile, engine_impl.h launch_cfg)
-      TORCH_CHECK(c[i] == ddl::CFG_KWAVE || c[i] == ddl::CFG_MF16 || c[i] == ddl::CFG_KW16 ||
-                      (c[i] >= 0 && c[i] < (big ? ddl::NUM_EVAL_TILE_CFGS : ddl::NUM_TILE_CFGS)),
-                  "tile config out of range");
-      e_.eval_cfg[i] = (int)c[i];
-    }
-  }
-  std::vector<int64_t> get_eval_cfg() const {
-    return std::vector<int64_t>(e_.eval_cfg, e_.eval_cfg + ddl::OP_COUNT);
+  static std::vector<int64_t> vec(const int (&a)[ddl::OP_COUNT]) {
+    return std::vector<int64_t>(a, a + ddl::OP_COUNT);
   }
   // the side stream exists only in the (slower, A/B) two-stream mode: every extra HIP stream
   // competes for the GPU_MAX_HW_QUEUES hardware queues
@@ -264,9 +258,9 @@ class PyEngine {
       c10::hip::HIPGuard guard(device_.index());
       e_.init_streams();
     }
-    e_.concurrent = on;
+    e_.sched.concurrent = on;
   }
-  void set_dual(bool on) { e_.dual = on; }
+  void set_dual(bool on) { e_.sched.dual = on; }
   // the same update as a one-piece optimizer tail that no launch takes: Engine::flush_tail's
   // stand-alone launch (tests)
   void flush_update_tail(int64_t kind, at::Tensor w, at::Tensor g, c10::optional<at::Tensor> m,
@@ -290,30 +284,28 @@ class PyEngine {
     e_.tail.add_piece(q);
     e_.tail.finish();
   }
-  // host counters of the dispatch branches (kernels/api.h enum Branch), by name in enum order
+  // host counters of the dispatch branches (kernels/schedule.h enum Branch), by name in enum order
   py::dict dispatch_hits() const {
     py::dict d;
-    for (int b = 0; b < ddl::BR_COUNT; ++b) d[ddl::Engine::branch_name(b)] = e_.branch_hits[b];
+    for (int b = 0; b < ddl::BR_COUNT; ++b) d[ddl::branch_name(b)] = e_.branch_hits[b];
     return d;
   }
   void reset_dispatch_hits() {
     for (int& h : e_.branch_hits) h = 0;
   }
   void set_wide_thr(int64_t t) {
-    e_.wide_thr = (int)std::max<int64_t>(1, t);
-    for (int i = 0; i < ddl::OP_COUNT; ++i) e_.wide[i] = e_.wide_thr;
+    e_.sched.wide_thr = (int)std::max<int64_t>(1, t);
+    for (int i = 0; i < ddl::OP_COUNT; ++i) e_.sched.wide[i] = e_.sched.wide_thr;
   }
   // per-op split-K reduce threshold: z > wide[op] -> separate reduce kernel, else in-launch
   void set_wide(std::vector<int64_t> w) {
     TORCH_CHECK((int)w.size() == ddl::OP_COUNT, "expected ", (int)ddl::OP_COUNT, " thresholds");
-    for (int i = 0; i < ddl::OP_COUNT; ++i) e_.wide[i] = (int)std::max<int64_t>(1, w[i]);
+    for (int i = 0; i < ddl::OP_COUNT; ++i) e_.sched.wide[i] = (int)std::max<int64_t>(1, w[i]);
   }
-  std::vector<int64_t> get_wide() const {
-    return std::vector<int64_t>(e_.wide, e_.wide + ddl::OP_COUNT);
-  }
+  std::vector<int64_t> get_wide() const { return vec(e_.sched.wide); }
   // bit op: the dual launch of op's layer dispatches its second problem first
-  void set_dual_bfirst(int64_t m) { e_.dual_bfirst = (int)m; }
-  int64_t get_dual_bfirst() const { return e_.dual_bfirst; }
+  void set_dual_bfirst(int64_t m) { e_.sched.dual_bfirst = (int)m; }
+  int64_t get_dual_bfirst() const { return e_.sched.dual_bfirst; }
 
   void set_keep_prob(double keep) {
     const double rate = 1.0 - keep;
@@ -323,12 +315,10 @@ class PyEngine {
 
   void set_splits(std::vector<int64_t> s) {
     TORCH_CHECK((int)s.size() == ddl::OP_COUNT, "expected ", (int)ddl::OP_COUNT, " split factors");
-    for (int i = 0; i < ddl::OP_COUNT; ++i) e_.splits[i] = (int)std::max<int64_t>(1, s[i]);
+    for (int i = 0; i < ddl::OP_COUNT; ++i) e_.sched.splits[i] = (int)std::max<int64_t>(1, s[i]);
     realloc();
   }
-  std::vector<int64_t> get_splits() const {
-    return std::vector<int64_t>(e_.splits, e_.splits + ddl::OP_COUNT);
-  }
+  std::vector<int64_t> get_splits() const { return vec(e_.sched.splits); }
   void forward(at::Tensor x, at::Tensor seed, bool train) {
     check_x(x);
     e_.forward(x.data_ptr<float>(), (int)x.size(0), seed_ptr(seed), train, cur_stream());
@@ -1159,6 +1149,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("get_cfg", &PyEngine::get_cfg)
       .def("set_eval_cfg", &PyEngine::set_eval_cfg)
       .def("get_eval_cfg", &PyEngine::get_eval_cfg)
+      .def("effective_cfg", [](const PyEngine& e) { return e.effective(true); })
+      .def("effective_eval_cfg", [](const PyEngine& e) { return e.effective(false); })
+      .def_static("op_has_cfg", [](int op, int cfg, bool train) {
+        return ddl::op_has_cfg(op, cfg, train);
+      })
       .def("set_concurrent", &PyEngine::set_concurrent)
       .def("set_dual", &PyEngine::set_dual)
       .def("flush_update_tail", &PyEngine::flush_update_tail, py::arg("kind"), py::arg("w"),
@@ -1171,12 +1166,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("nesterov") = false)
       .def("dispatch_hits", &PyEngine::dispatch_hits)
       .def("reset_dispatch_hits", &PyEngine::reset_dispatch_hits)
-      .def("set_fc_wgrad_defer", [](PyEngine& e, bool on) { e.raw()->fc_wgrad_defer = on; })
-      .def("fc_wgrad_defer", [](PyEngine& e) { return e.raw()->fc_wgrad_defer; })
-      .def("set_conv1_direct", [](PyEngine& e, bool on) { e.raw()->conv1_direct = on; })
-      .def("conv1_direct", [](PyEngine& e) { return e.raw()->conv1_direct; })
-      .def("set_conv1_wgrad_direct", [](PyEngine& e, bool on) { e.raw()->conv1_wgrad_direct = on; })
-      .def("conv1_wgrad_direct", [](PyEngine& e) { return e.raw()->conv1_wgrad_direct; })
+      .def("set_fc_wgrad_defer", [](PyEngine& e, bool on) { e.raw()->sched.fc_wgrad_defer = on; })
+      .def("fc_wgrad_defer", [](PyEngine& e) { return e.raw()->sched.fc_wgrad_defer; })
+      .def("set_conv1_direct", [](PyEngine& e, bool on) { e.raw()->sched.conv1_direct = on; })
+      .def("conv1_direct", [](PyEngine& e) { return e.raw()->sched.conv1_direct; })
+      .def("set_conv1_wgrad_direct", [](PyEngine& e, bool on) { e.raw()->sched.conv1_wgrad_direct = on; })
+      .def("conv1_wgrad_direct", [](PyEngine& e) { return e.raw()->sched.conv1_wgrad_direct; })
       .def("set_wide_thr", &PyEngine::set_wide_thr)
       .def("set_wide", &PyEngine::set_wide)
       .def("set_dual_bfirst", &PyEngine::set_dual_bfirst)

@@ -19,12 +19,25 @@
 
 #include "clip_ranges.h"
 #include "runtime/session.h"
+#include "schedule.h"
 #include "scratch.h"
 #include "tail.h"
 
 namespace ddl {
 
 class ShmMailbox;
+
+// A boolean DDL_* environment variable: `def` when unset; when set, off only for a leading '0'
+// (only_1: on only for a leading '1')
+inline bool env_flag(const char* name, bool def, bool only_1 = false) {
+  const char* e = getenv(name);
+  return !e ? def : only_1 ? e[0] == '1' : e[0] != '0';
+}
+// DDL_XGMI_TIMEOUT_S: the bound of every xGMI wait and of the runner's READY gate, in seconds
+inline double xgmi_timeout_s(double def) {
+  const char* e = getenv("DDL_XGMI_TIMEOUT_S");
+  return e ? atof(e) : def;
+}
 
 // ---- optimizer (optim.hip) -------------------------------------------------------------------
 // One update of span s from gradient g under rule r (update.h) with step size `step`: the 16-B
@@ -149,93 +162,48 @@ void launch_mfma_peak(float* out, int blocks, int iters, hipStream_t st, int kin
 void launch_gemm_nomem(float* out, int M, int N, int K, int splits, void* slab, int* tickets,
                        hipStream_t st);
 
-// ---- the CNN step engine (engine.hip) --------------------------------------------------------
-// GEMM-shaped ops, in SURVEY.md §2.6 order.  Index into Engine::splits / Engine::cfg.
-enum Op {
-  OP_CONV1_FWD = 0, OP_CONV2_FWD, OP_CONV3_FWD, OP_CONV4_FWD, OP_FC1_FWD, OP_FC2_FWD,
-  OP_FC2_DGRAD, OP_FC2_WGRAD, OP_FC1_DGRAD, OP_FC1_WGRAD,
-  OP_CONV4_DGRAD, OP_CONV4_WGRAD, OP_CONV3_DGRAD, OP_CONV3_WGRAD,
-  OP_CONV2_DGRAD, OP_CONV2_WGRAD, OP_CONV1_WGRAD,
-  OP_COUNT
-};
-
-// Block-tile configurations selectable per op at run time (gemm.h template args
-// <BM, BN, BK=32, WM, WN>): 0 = 64x64 (1 wave 64x64), 1 = 128x64 (2 waves 64x64),
-// 2 = 64x32 (1 wave), 3 = 32x32 (1 wave), 4 = 32x64 (1 wave),
-// 5 = 32x32 with BK = 16 and the software-pipelined main loop (1 wave),
-// 6 = 64x64 (4 waves of 32x32), 7 = 64x32 (2 waves of 32x32), 8 = 32x64 (2 waves of 32x32):
-// multi-wave blocks share each staged operand tile between waves (half the L1/L2 bytes per
-// MFMA of one-wave 32x32 blocks at 64x64), at one barrier per K tile.
-constexpr int NUM_TILE_CFGS = 9;
-// Eval-only large-M configs (conv forward ops at 10k-row test-set chunks; no split-K, so only
-// instantiated for those ops): 9 = 128x128 (2x2 waves of 64x64), 10 = 128x64 (2x2 waves of
-// 64x32), 11 = 256x64 (4x1 waves of 64x64), 12 = 128x128 (4x1 waves of 32x128).
-constexpr int NUM_EVAL_TILE_CFGS = 13;
-// training-only: 32x32 one-wave tiles with the K range split over the waves of ONE workgroup
-// (gemm.h gemm_kwave_kernel; `splits` picks 4 / 8 / 16 waves); fc layers only
-constexpr int CFG_KWAVE = 13;
-// training-only: the one-wave 32x32x32 tile on v_mfma_f32_16x16x4_f32 with LDS-DMA staging
-// (gemm.h GemmTile::mainloop_dma16); conv2-4 forward / data gradient / weight gradient only
-// (other ops fall back to config 3)
-constexpr int CFG_MF16 = 14;
-// training-only: the K-wave launch on 16-row tiles (kwave16.h gemm_kw16_kernel; `splits` picks 4 /
-// 8 / 16 waves); the fc forwards only (other ops fall back to config 3)
-constexpr int CFG_KW16 = 15;
-// (configs 16-20 — one-wave multi-fragment LDS-DMA tiles and the 32x32 ring tiles — were
-// measured in round 5, never won a launch and were removed: docs/DESIGN.md)
-
-// The run-time choices of a backward segment's launches (engine_impl.h, engine.hip), counted on
-// the host where each commits to its launches (Engine::branch_hits; tests prove with them that a
-// schedule reached the branch it was written for: configs fall back silently).  Names:
-// Engine::branch_name.
-enum Branch {
-  // an fc pair (data + weight gradient of fc2 / fc1): the packed launch with the weight gradient
-  // left to the conv4 dual launch, the packed launch that keeps it, the one-wave dual launch,
-  // back to back
-  BR_FC_PACK_DEFERRED = 0, BR_FC_PACK_KEPT, BR_FC_DUAL, BR_FC_BACK_TO_BACK,
-  // conv4's pair: the dual launch with the deferred fc weight gradients (FcWgradAux) or with the
-  // optimizer tail alone (TailAux); back to back with fc weight gradients left to flush_fc_wgrad,
-  // or with none pending
-  BR_CONV4_DUAL_FC_WGRAD, BR_CONV4_DUAL_TAIL, BR_CONV4_BACK_TO_BACK_FLUSH, BR_CONV4_BACK_TO_BACK,
-  BR_CONV3_DUAL, BR_CONV3_BACK_TO_BACK,
-  // conv2's pair inside the unfused sequence of segment 3
-  BR_CONV2_DUAL, BR_CONV2_BACK_TO_BACK,
-  // segment 3 fused (dual_then_b): conv1's direct kernel with conv2's reduce riding in it or with
-  // none pending; the reduce fused with conv1's GEMM (launch_reduce_with_gemm) or its refusal
-  // (launch_reduce, then run_op)
-  BR_SEG3_DIRECT_REDUCE, BR_SEG3_DIRECT, BR_SEG3_REDUCE_GEMM, BR_SEG3_REDUCE_REFUSED,
-  BR_SEG3_UNFUSED,            // run_dual_inst + run_op
-  BR_TAIL_STANDALONE,         // flush_tail issued update launches of its own
-  BR_TAIL_CONSUMED,           // a launch took the pending tail (dual, pack, FcWgradAux)
-  BR_CONCURRENT,              // a segment in the two-stream mode
-  BR_COUNT
-};
-
+// ---- the CNN step engine (engine.hip; its ops, configs and launch decisions: schedule.h) ------
 struct Engine {
+  // ---- the schedule (input): the tuned defaults with the DDL_* overrides on top
+  Schedule sched;
+  uint32_t thr24 = 0;        // dropout threshold (train)
+  uint32_t seed_value = 0;   // dropout seed used when a step is given no device seed word
+  float inv_keep = 1.f;
+
+  // ---- the pending hand-offs: work one launch leaves to the next
+  // optimizer tail (tail.h) for the next dual launch; consumed (and cleared) by it, or by
+  // flush_tail() as a launch of its own when no dual launch takes it
+  UpdTail tail;
+  // the LAST segment's update (W = 1 tail path): conv1's part applied by its weight-gradient
+  // reduce epilogue, the rest as tail blocks of that launch (engine_impl.h dual_then_b).
+  // Cleared when taken; the runner launches it as before when it is still pending.
+  UpdTail final_upd;
+  // fc3 weight gradient still to compute (fused head kernel ran): taken by the fc2 dual launch
+  int head_wgrad_pending = 0;
+  // fc weight gradients the packed launches left to the conv4 dual launch (bit 0: fc2, 1: fc1)
+  int fc_wgrad_pending = 0;
+  // fc2 forward's split-K partials left to the head kernel (fc2_in_head); null: h2 is final
+  const float* fc2_slab = nullptr;
+  int fc2_S = 0, fc2_gx = 0, fc2_ntiles = 0;
+  // the pending tail, handed to the launch that carries it
+  UpdTail take_tail() {
+    const UpdTail t = tail;
+    if (t.nblocks > 0) hit(BR_TAIL_CONSUMED);
+    tail = UpdTail();
+    return t;
+  }
+  // stand-alone optimizer launches flush_tail() has issued for update tails no launch took
+  // (host counter, diagnostic: SyncRunner::update_launches)
+  int update_launches = 0;
+  // host counters of the dispatch branches taken since the last reset (enum Branch)
+  int branch_hits[BR_COUNT] = {};
+  void hit(Branch b) { ++branch_hits[b]; }
+
+  // ---- the buffers
   const float* P[14] = {};   // parameter tensors v0..v13 (any flat layout)
   float* G[14] = {};         // gradient tensors v0..v13
   int max_batch = 0;         // activation buffers sized for this batch
   int train_batch = 0;       // slab sized for this batch with the current splits/cfgs
-  int splits[OP_COUNT];
-  int cfg[OP_COUNT];
-  int eval_cfg[OP_COUNT];    // tile configs of the no-split eval forward (train = false)
-  int wide_thr = 1;          // default split count above which the separate wide reduce is used
-  int wide[OP_COUNT];        // per op: z > wide[op] -> separate wide reduce (mode 2), else the
-                             // in-launch last-arriver reduction (mode 1)
-  uint32_t thr24 = 0;        // dropout threshold (train)
-  uint32_t seed_value = 0;   // dropout seed used when a step is given no device seed word
-  float inv_keep = 1.f;
-  // weight-gradient GEMMs on a second stream.  Off by default: a cross-queue event wait costs
-  // tens of microseconds of GPU idle on MI355X/ROCm (step timelines), more than the overlap
-  // gains; dgrad/wgrad concurrency comes from fused dual-problem launches instead.
-  bool concurrent = false;
-  bool dual = true;          // single stream: dgrad + wgrad of a layer in one launch
-  // bit op: that dual launch dispatches its second problem first.  conv2's (weight gradient
-  // split 32 ways, the longer pole) measured 0.3663 -> 0.3650 ms/step; conv4's / conv3's worse
-  // (their data gradients are the longer poles; conv4's stream-K loses its XCD-major numbering).
-  int dual_bfirst = (1 << OP_CONV2_DGRAD) | (1 << OP_CONV3_DGRAD);
-  int dual_order(int op) const { return (dual_bfirst >> op) & 1; }
-
   // workspace carve-out
   float *p1 = nullptr, *p2 = nullptr, *p3 = nullptr, *p4 = nullptr, *h1 = nullptr, *h2 = nullptr;
   float *dlog = nullptr, *loss = nullptr, *dpre2fc = nullptr, *dpre1fc = nullptr;
@@ -245,63 +213,8 @@ struct Engine {
   size_t slab_floats = 0;
   SplitScratch scratch[2];   // [0] main stream, [1] weight-gradient stream
   static constexpr int kMaxTickets = 8192;
-
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  // optimizer tail (tail.h) for the next dual launch; consumed (and cleared) by it, or by
-  // flush_tail() as a launch of its own when no dual launch takes it
-  UpdTail tail;
-  // the LAST segment's update (W = 1 tail path): conv1's part applied by its weight-gradient
-  // reduce epilogue, the rest as tail blocks of that launch (engine_impl.h dual_then_b).
-  // Cleared when taken; the runner launches it as before when it is still pending.
-  UpdTail final_upd;
-  // stand-alone optimizer launches flush_tail() has issued for update tails no launch took
-  // (host counter, diagnostic: SyncRunner::update_launches)
-  int update_launches = 0;
-  // host counters of the dispatch branches taken since the last reset (enum Branch)
-  int branch_hits[BR_COUNT] = {};
-  static const char* branch_name(int b);
-  void hit(Branch b) { ++branch_hits[b]; }
-  // the pending tail, handed to the launch that carries it
-  UpdTail take_tail() {
-    const UpdTail t = tail;
-    if (t.nblocks > 0) hit(BR_TAIL_CONSUMED);
-    tail = UpdTail();
-    return t;
-  }
-  // eval forward: conv2 on the tap-skipping K map (DDL_EVAL_KMAP2=0: the image-major GEMM)
-  bool eval_kmap2 = [] {
-    const char* e = getenv("DDL_EVAL_KMAP2");
-    return !e || e[0] != '0';
-  }();
-  // conv1 forward on the direct LDS-staged kernel (conv1.hip) instead of the GEMM engine's
-  // gather-bound K = 25 launch.  DDL_CONV1_DIRECT=0: the GEMM path
-  bool conv1_direct = [] {
-    const char* e = getenv("DDL_CONV1_DIRECT");
-    return !e || e[0] != '0';
-  }();
-  // conv1's weight gradient on the direct kernel with its in-launch reduce (conv1.h), riding
-  // with conv2's weight-gradient reduce, instead of the GEMM launch + wide reduce launch.
-  // DDL_CONV1_WGRAD_DIRECT=0: the GEMM path
-  bool conv1_wgrad_direct = [] {
-    const char* e = getenv("DDL_CONV1_WGRAD_DIRECT");
-    return !e || e[0] != '0';
-  }();
-  // fc3 weight gradient still to compute (fused head kernel ran): taken by the fc2 dual launch
-  int head_wgrad_pending = 0;
-  // the fc backward's packed launches leave the fc weight gradients (bit 0: fc2, bit 1: fc1) to
-  // the conv4 dual launch (engine_impl.h FcWgradAux); false: they stay in the packs
-  bool fc_wgrad_defer = true;
-  int fc_wgrad_pending = 0;
-  // fc2 forward's split-K partials whose reduce + epilogue the head kernel runs (the step's
-  // forward with defer_fc2, one-wave 32x32 split-K in mode 2): one launch fewer per step.
-  // DDL_FC2_REDUCE_IN_HEAD=0 keeps the separate reduce launch.
-  bool fc2_in_head = [] {
-    const char* e = getenv("DDL_FC2_REDUCE_IN_HEAD");
-    return !e || e[0] != '0';
-  }();
-  const float* fc2_slab = nullptr;  // pending partials (null: h2 is final)
-  int fc2_S = 0, fc2_gx = 0, fc2_ntiles = 0;
 
   Engine();
   ~Engine();
@@ -963,10 +876,7 @@ class SyncRunner {
   bool all_local_ = false;
   UpdatePlan plan_;  // all_local_: where the LOCAL updates go (update_plan.h)
   bool use_tail_ = true;
-  bool final_in_reduce_ = [] {
-    const char* e = getenv("DDL_FINAL_IN_REDUCE");
-    return !e || e[0] != '0';
-  }();
+  bool final_in_reduce_ = env_flag("DDL_FINAL_IN_REDUCE", true);
 
  public:
   void set_ready_flags(int mode) { ready_flags_ = mode; }

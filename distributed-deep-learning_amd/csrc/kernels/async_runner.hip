@@ -63,8 +63,8 @@ AsyncRunner::AsyncRunner(Engine* eng, AsyncPeer* peer, int world, int rank, int 
   if ((int)seg_of_ps.size() != P) throw std::invalid_argument("async runner: one segment per PS");
   // (A/B switches: DDL_ASYNC_GATE=0 waits for the round on the host, DDL_ASYNC_TAIL=0 pushes
   // with kernels of their own instead of tail blocks)
-  if (const char* g = getenv("DDL_ASYNC_GATE")) gate_ = g[0] != '0';
-  if (const char* t = getenv("DDL_ASYNC_TAIL")) use_tail_ = t[0] != '0';
+  gate_ = env_flag("DDL_ASYNC_GATE", gate_);
+  use_tail_ = env_flag("DDL_ASYNC_TAIL", use_tail_);
   for (int p = 0; p < P; ++p) {
     if (seg_of_ps[p] < 0 || seg_of_ps[p] >= kSegments)
       throw std::invalid_argument("async runner: PS segment out of range");

@@ -1,12 +1,16 @@
 // The CNN step engine: every forward / backward kernel launch of one worker step.
 //
 // Reference step: sess.run(grads) on the TF runtime, 14 host round trips
-// to push, 14 to pull.  Here a step is ~20 GEMM-engine launches + 2 head kernels, all
-// buffers preallocated (graph-capturable: no malloc, no sync).  The backward is split
-// into 4 segments so the host can push a segment's gradients on a side stream while the
-// next segment computes (SURVEY.md §5.8 bucket plan); inside a segment the weight-gradient
-// GEMM runs on a second stream concurrently with the data-gradient GEMM that feeds the
-// next segment (fork/join events, captured as parallel graph branches).
+// to push, 14 to pull.  Here a training step at one worker is 16 launches on one stream, all
+// buffers preallocated (graph-capturable: no malloc, no sync): the forward, the fused loss head
+// and four backward segments in which each layer's data- and weight-gradient GEMMs share one
+// dual or packed launch that also carries the previous segment's optimizer tail (the last
+// segment's update rides in conv1's weight-gradient launch).  The backward is split into
+// segments so the host can push a segment's gradients on a side stream while the next segment
+// computes (SURVEY.md §5.8 bucket plan).  What each launch is comes from the schedule
+// (schedule.h: Schedule, choose_pair, choose_seg3).  The two-stream mode (Schedule::concurrent:
+// weight-gradient GEMMs on a second stream, fork/join events per segment) is the A/B option it
+// was measured against; it is slower and off by default.
 #include <stdlib.h>
 #include <string.h>
 
@@ -18,66 +22,13 @@
 
 namespace ddl {
 
-Engine::Engine() {
-  // {tile config, split-K} per op: whole-step coordinate-descent tune
-  // (scripts/step_tune.py over the scripts/op_bench.py per-op sweep) on one MI355X, batch 100,
-  // single-stream backward with dual dgrad+wgrad launches: fwd+bwd 367 us (was 449 us)
-  // (round 2, after the halo layout and the batch-minor weight-gradient enumeration: conv2
-  // weight gradient on the basic BK 32 loop instead of the pipelined BK 16 one, 342.8 ->
-  // 336.5 us, profiles/r2_runner_tune_halo.log)
-  // fc1 forward on the K-wave launch (8 waves per workgroup, LDS reduction, no reduce launch):
-  // 313.4 -> 310.6 us (profiles/r2_runner_tune_kwave.log); fc1 data gradient as the K-wave
-  // half of one packed launch with its weight gradient (gemm_pack_kernel, 4 waves), instead
-  // of the one-wave dual launch + wide reduce: 308.7 -> 304.4 us (profiles/r2_runner_tune_pack.log)
-  // (round 3, after the direct conv1 kernels: fc2 data gradient on the K-wave half of a packed
-  // launch with its weight gradient, like fc1's: 292.8 -> 291.5 us, profiles/r3_runner_tune.log)
-  // (round 5, scripts/sched_ab.py on one MI355X, 5 alternating rounds of 300 steps: conv4
-  // weight gradient and conv2 data gradient on the 16x16x4 MFMA tile (config 14), conv4 weight
-  // gradient split 8: 295.3 -> 293.0 us, profiles/r5_sched_ab_mf16.log; then conv3 weight
-  // gradient on config 14 too: 293.5 -> 292.7 us, profiles/r5_sched_ab_conv3w.log — conv2's
-  // weight gradient on it loses 6 us)
-  // (round 6: fc1's and fc2's forwards on the 16-row K-wave launch, 8 waves — fc2 then writes h2
-  // itself and the head reads it instead of fc2's split-K partials: 260.7-261.0 -> 259.1-259.4
-  // us/step, 4 interleaved rounds, profiles/r6_sched_ab_kw16.log)
-  static const int defc[OP_COUNT] = {3, 3, 3, 3, CFG_KW16, CFG_KW16, CFG_KWAVE, 5, CFG_KWAVE, 5,
-                                     3, CFG_MF16, 3, CFG_MF16, CFG_MF16, 3, 3};
-  // (re-tuned in the real step with scripts/sched_ab.py after the compact 52-row conv3
-  // enumeration and the wgrad row decode: conv3 forward split 4 + in-launch reduce instead of
-  // stream-K 3072 workers, 372.4 -> 369.5 us; conv4 weight gradient split 4 instead of 8,
-  // 370.5 -> 368.0 us; conv4 data gradient 2560 stream-K workers and conv3 weight gradient
-  // split 12, 365.2 -> 362.3 us)
-  // (round 2, with the tap-skipping K maps of conv3/conv4: conv4 data gradient split-K 4 with
-  // a separate reduce instead of stream-K over the full K, 322.2 -> 313.3 us,
-  // profiles/r2_runner_tune_kmap.log)
-  // (round 3, conv forwards on the LDS-DMA main loop: conv2 / conv3 / conv4 forward split-K
-  // 3 / 3 / 6 instead of 2 / 4 / 8, 302.5 -> 299.0 us fwd+bwd, scripts/sched_ab.py
-  // --splits-variants, profiles/r3_sched_ab_ldsdma.log)
-  // (round 6, after the row-wise data-gradient epilogues made the last arriver cheap: conv4's
-  // data gradient split-K 5 with the in-launch reduce instead of 4 + the separate wide reduce,
-  // conv3's split-K 5 instead of 8, and the conv3 dual dispatching its weight-gradient blocks
-  // first (api.h dual_bfirst): 279.2 -> 267.7 us/step, scripts/sched_ab.py,
-  // profiles/r6_sched_ab_grid.log; then conv2's weight gradient split-K 48 instead of 32 and
-  // conv4's 6 instead of 8: 267.2 -> 264.8, profiles/r6_sched_ab_wgrad.log; conv4's forward
-  // split-K 5 instead of 6 once the last arriver sums its partials in one batched round per 4:
-  // 264.4 -> 262.9, profiles/r6_runner_tune.log, r6_sched_ab_zb.log)
-  static const int defs[OP_COUNT] = {1, 3, 3, 5, 8, 8, 4, 1, 4, 1, 5, 6, 5, 12, 4, 48, 1024};
-  // split-K reduce in-launch (last arriver) for these ops, separate wide-reduce kernel otherwise
-  static const bool inl[OP_COUNT] = {0, 1, 1, 1, 0, 0, 1, 0, 0, 0, 1, 1, 1, 1, 1, 0, 0};
-  memcpy(cfg, defc, sizeof(defc));
-  memcpy(eval_cfg, defc, sizeof(defc));
-  // eval forward at 10k-row chunks (scripts/eval_sweep.py, after the compact conv3 rows):
-  // conv2-4 on 4-wave 64x64 blocks, full test-set eval 6.76 -> 6.66 ms (106 TF); round 2:
-  // conv3 on the eval-only 128x128 block (2x2 waves of 64x64), 6.62 -> 6.53 ms (108 TF) —
-  // the larger eval tiles (9-12) gain at most 1.4 %, so the eval is bound by the main loop,
-  // not by tile shape (profiles/r2_eval_sweep_big_tiles.log)
-  // round 3 (scripts/eval_sweep.py on the current build, profiles/r3_eval_sweep.log): the
-  // one-wave 64x64 tile (4 fragments per wave, no LDS sharing between waves) for conv2-4,
-  // full test-set eval 5.04 -> 4.64 ms
-  eval_cfg[OP_CONV2_FWD] = 0;
-  eval_cfg[OP_CONV3_FWD] = 0;
-  eval_cfg[OP_CONV4_FWD] = 0;
-  memcpy(splits, defs, sizeof(defs));
-  for (int op = 0; op < OP_COUNT; ++op) wide[op] = inl[op] ? (1 << 20) : 1;
+Engine::Engine() : sched(Schedule::defaults()) {
+  // DDL_EVAL_KMAP2=0: the image-major GEMM; DDL_CONV1_DIRECT=0 / DDL_CONV1_WGRAD_DIRECT=0: the
+  // GEMM paths; DDL_FC2_REDUCE_IN_HEAD=0 keeps fc2's separate reduce launch
+  sched.eval_kmap2 = env_flag("DDL_EVAL_KMAP2", true);
+  sched.conv1_direct = env_flag("DDL_CONV1_DIRECT", true);
+  sched.conv1_wgrad_direct = env_flag("DDL_CONV1_WGRAD_DIRECT", true);
+  sched.fc2_in_head = env_flag("DDL_FC2_REDUCE_IN_HEAD", true);
 }
 
 Engine::~Engine() {
@@ -118,32 +69,16 @@ void Engine::op_shape(int op, int B, int* M, int* N, int* K) {
   *M = m; *N = n; *K = k;
 }
 
-#define TILE_0 64, 64, 32, 1, 1
-#define TILE_1 128, 64, 32, 2, 1
-#define TILE_2 64, 32, 32, 1, 1
-#define TILE_3 32, 32, 32, 1, 1
-#define TILE_4 32, 64, 32, 1, 1
-#define TILE_5 32, 32, 16, 1, 1   // software-pipelined main loop (gemm.h GemmTile::PIPE)
-#define TILE_6 64, 64, 32, 2, 2   // 4 waves of 32x32 sharing one LDS-staged 64x64 block tile
-#define TILE_7 64, 32, 32, 2, 1   // 2 waves of 32x32 along M
-#define TILE_8 32, 64, 32, 1, 2   // 2 waves of 32x32 along N
-
-static size_t slab_need(int c, int M, int N, int K, int s) {
-  switch (c) {
-    // reduces in LDS; an op without a K-wave instantiation falls back to the 32x32 split-K
-    // launch with the same split factor (engine_impl.h launch_cfg), so size for that
-    case CFG_KWAVE: return gemm_slab_f4<TILE_3>(M, N, K, s);
-    case CFG_MF16: return gemm_slab_f4<TILE_3>(M, N, K, s);  // same 32x32 partial layout
-    case CFG_KW16: return gemm_slab_f4<TILE_3>(M, N, K, s);  // (fallback: 32x32 split-K)
-    case 0: return gemm_slab_f4<TILE_0>(M, N, K, s);
-    case 1: return gemm_slab_f4<TILE_1>(M, N, K, s);
-    case 2: return gemm_slab_f4<TILE_2>(M, N, K, s);
-    case 3: return gemm_slab_f4<TILE_3>(M, N, K, s);
-    case 4: return gemm_slab_f4<TILE_4>(M, N, K, s);
-    case 5: return gemm_slab_f4<TILE_5>(M, N, K, s);
-    case 6: return gemm_slab_f4<TILE_6>(M, N, K, s);
-    case 7: return gemm_slab_f4<TILE_7>(M, N, K, s);
-    default: return gemm_slab_f4<TILE_8>(M, N, K, s);
+// float4 partial-slab elements op `op` needs on config c (a K-wave launch reduces in LDS; it is
+// sized as the 32x32 tile)
+static size_t slab_need(int op, int c, int M, int N, int K, int s) {
+  c = effective_cfg(op, c, true);
+  switch (c == CFG_KWAVE || c == CFG_KW16 ? 3 : c) {
+#define DDL_SLAB(id, bm, bn, bk, wm, wn, v) \
+  case id: return gemm_slab_f4<bm, bn, bk, wm, wn>(M, N, K, s);
+    TILE_ALL(DDL_SLAB)
+#undef DDL_SLAB
+    default: return 0;
   }
 }
 
@@ -158,7 +93,7 @@ size_t Engine::slab_floats_needed(int B) const {
     for (int op = 0; op < OP_COUNT; ++op) {
       int M, N, K;
       op_shape(op, b, &M, &N, &K);
-      const size_t f = 4 * slab_need(cfg[op], M, N, K, splits[op]);
+      const size_t f = 4 * slab_need(op, sched.cfg[op], M, N, K, sched.splits[op]);
       if (f > mx) mx = f;
     }
   return mx;
@@ -204,12 +139,12 @@ void Engine::bind_workspace(void* base) {
 
 void Engine::run_op(int op, const float* x, int B, const uint32_t* seed, bool train,
                     hipStream_t st, int si) {
-  if (op == OP_CONV1_FWD && conv1_direct) {
+  if (op == OP_CONV1_FWD && sched.conv1_direct) {
     launch_conv1_fwd(x, P[0], P[1], p1, train ? c1 : nullptr, B, st);
     return;
   }
   // (the dual path fuses it with conv2's weight-gradient reduce: engine_impl.h dual_then_b)
-  if (op == OP_CONV1_WGRAD && conv1_wgrad_direct &&
+  if (op == OP_CONV1_WGRAD && sched.conv1_wgrad_direct &&
       conv1_wgrad_fits(B, slab_floats, scratch[si].max_tiles)) {
     launch_conv1_wgrad_only(x, d1, B, G[0], G[1], static_cast<float*>(scratch[si].slab),
                             scratch[si].tickets, st);
@@ -249,16 +184,6 @@ void Engine::flush_tail(hipStream_t st) {
   tail = UpdTail();
 }
 
-const char* Engine::branch_name(int b) {
-  static const char* const names[BR_COUNT] = {
-      "fc_pack_deferred", "fc_pack_kept", "fc_dual", "fc_back_to_back",
-      "conv4_dual_fc_wgrad", "conv4_dual_tail", "conv4_back_to_back_flush", "conv4_back_to_back",
-      "conv3_dual", "conv3_back_to_back", "conv2_dual", "conv2_back_to_back",
-      "seg3_direct_reduce", "seg3_direct", "seg3_reduce_gemm", "seg3_reduce_refused",
-      "seg3_unfused", "tail_standalone", "tail_consumed", "concurrent"};
-  return b >= 0 && b < BR_COUNT ? names[b] : "";
-}
-
 void Engine::flush_fc_wgrad(const float* x, int B, const uint32_t* seed, hipStream_t st) {
   const int pend = fc_wgrad_pending;
   fc_wgrad_pending = 0;
@@ -277,7 +202,7 @@ void Engine::forward(const float* x, int B, const uint32_t* seed, bool train, hi
   fc2_slab = nullptr;  // (a deferred fc2 reduce nobody took: this forward rewrites h2 anyway)
   fc_wgrad_pending = 0;  // (likewise: their inputs are about to be rewritten)
   for (int op = OP_CONV1_FWD; op < OP_FC2_FWD; ++op) run_op(op, x, B, seed, train, st, 0);
-  if (!(train && defer_fc2 && fc2_in_head && !concurrent && run_fc2_deferred(*this, x, B, seed, st)))
+  if (!(train && defer_fc2 && sched.fc2_in_head && !sched.concurrent && run_fc2_deferred(*this, x, B, seed, st)))
     run_op(OP_FC2_FWD, x, B, seed, train, st, 0);
 }
 
@@ -302,37 +227,30 @@ void Engine::wgrad(int op, const float* x, int B, const uint32_t* seed, hipStrea
   run_op(op, x, B, seed, true, side, 1);
 }
 
+// pair I of segment S (schedule.h kSegment) as one launch or back to back
+template <int S, int I>
+static void run_pair(Engine& e, const float* x, int B, const uint32_t* seed, hipStream_t st) {
+  run_dual_inst<kSegment[S].pair[I].dgrad, kSegment[S].pair[I].wgrad>(e, x, B, seed, st);
+}
+
 void Engine::backward_segment(int s, const float* x, const int64_t* labels, int B,
                               const uint32_t* seed, hipStream_t st) {
-  if (concurrent && side) {  // weight gradients on the side stream (fork/join per segment)
+  if (s < 0 || s >= kSegments) return;
+  if (sched.concurrent && side) {  // weight gradients on the side stream (fork/join per segment)
     hit(BR_CONCURRENT);
     flush_tail(st);
     flush_fc2(seed, B, st);
-    switch (s) {
-      case 0:
-        launch_head_fwd(h2, P[12], P[13], labels, B, dlog, loss, nullptr, st);
-        launch_head_bwd(h2, P[12], dlog, B, seed, seed_value, thr24, inv_keep, G[12], G[13],
-                        dpre2fc, st);
-        wgrad(OP_FC2_WGRAD, x, B, seed, st);
-        run_op(OP_FC2_DGRAD, x, B, seed, true, st, 0);
-        wgrad(OP_FC1_WGRAD, x, B, seed, st);
-        run_op(OP_FC1_DGRAD, x, B, seed, true, st, 0);
-        break;
-      case 1:
-        wgrad(OP_CONV4_WGRAD, x, B, seed, st);
-        run_op(OP_CONV4_DGRAD, x, B, seed, true, st, 0);
-        break;
-      case 2:
-        wgrad(OP_CONV3_WGRAD, x, B, seed, st);
-        run_op(OP_CONV3_DGRAD, x, B, seed, true, st, 0);
-        break;
-      case 3:
-        wgrad(OP_CONV2_WGRAD, x, B, seed, st);
-        run_op(OP_CONV2_DGRAD, x, B, seed, true, st, 0);
-        wgrad(OP_CONV1_WGRAD, x, B, seed, st);
-        break;
-      default: break;
+    if (s == 0) {
+      launch_head_fwd(h2, P[12], P[13], labels, B, dlog, loss, nullptr, st);
+      launch_head_bwd(h2, P[12], dlog, B, seed, seed_value, thr24, inv_keep, G[12], G[13],
+                      dpre2fc, st);
     }
+    const Segment& g = kSegment[s];
+    for (int i = 0; i < g.npairs; ++i) {
+      wgrad(g.pair[i].wgrad, x, B, seed, st);
+      run_op(g.pair[i].dgrad, x, B, seed, true, st, 0);
+    }
+    if (g.then >= 0) wgrad(g.then, x, B, seed, st);
     join(st);
     return;
   }
@@ -351,19 +269,19 @@ void Engine::backward_segment(int s, const float* x, const int64_t* labels, int 
                           loss, dpre2fc, st);
       }
       head_wgrad_pending = 1;
-      run_dual_inst<OP_FC2_DGRAD, OP_FC2_WGRAD>(*this, x, B, seed, st);
+      run_pair<0, 0>(*this, x, B, seed, st);
       flush_head_wgrad(B, st);
-      run_dual_inst<OP_FC1_DGRAD, OP_FC1_WGRAD>(*this, x, B, seed, st);
+      run_pair<0, 1>(*this, x, B, seed, st);
       break;
     case 1:
-      run_dual_inst<OP_CONV4_DGRAD, OP_CONV4_WGRAD>(*this, x, B, seed, st);
+      run_pair<1, 0>(*this, x, B, seed, st);
       flush_fc_wgrad(x, B, seed, st);  // (a conv4 pair that ran back to back took none of them)
       break;
-    case 2: run_dual_inst<OP_CONV3_DGRAD, OP_CONV3_WGRAD>(*this, x, B, seed, st); break;
-    case 3:
-      run_dual_then_inst<OP_CONV2_DGRAD, OP_CONV2_WGRAD, OP_CONV1_WGRAD>(*this, x, B, seed, st);
+    case 2: run_pair<2, 0>(*this, x, B, seed, st); break;
+    default:
+      run_dual_then_inst<kSegment[3].pair[0].dgrad, kSegment[3].pair[0].wgrad, kSegment[3].then>(
+          *this, x, B, seed, st);
       break;
-    default: break;
   }
 }
 

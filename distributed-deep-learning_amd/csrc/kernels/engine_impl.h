@@ -16,57 +16,39 @@
 
 namespace ddl {
 
-#define TILE_0 64, 64, 32, 1, 1
-#define TILE_1 128, 64, 32, 2, 1
-#define TILE_2 64, 32, 32, 1, 1
-#define TILE_3 32, 32, 32, 1, 1
-#define TILE_4 32, 64, 32, 1, 1
-#define TILE_5 32, 32, 16, 1, 1   // software-pipelined main loop (gemm.h GemmTile::PIPE)
-#define TILE_6 64, 64, 32, 2, 2   // 4 waves of 32x32 sharing one LDS-staged 64x64 block tile
-#define TILE_7 64, 32, 32, 2, 1   // 2 waves of 32x32 along M
-#define TILE_8 32, 64, 32, 1, 2   // 2 waves of 32x32 along N
-// eval-only (conv forward, large M)
-#define TILE_9 128, 128, 32, 2, 2
-#define TILE_10 128, 64, 32, 2, 2
-#define TILE_11 256, 64, 32, 4, 1
-#define TILE_12 128, 128, 32, 4, 1
-// training: one-wave 32x32x32 on 16x16x4 MFMAs with LDS-DMA staging (CFG_MF16)
-#define TILE_14 32, 32, 32, 1, 1, 1
+// gemm.h TileCfg of tile ID of schedule.h's list, and launch_gemm on it
+template <int ID> struct TileOfT;
+#define DDL_TILE(id, ...) \
+  template <> struct TileOfT<id> { using T = TileCfg<__VA_ARGS__>; };
+TILE_ALL(DDL_TILE)
+#undef DDL_TILE
+template <int ID> using TileOf = typename TileOfT<ID>::T;
+template <int ID, class P>
+inline void launch_tile(const P& p, int s, int wide_thr, const SplitScratch& sc, hipStream_t st,
+                        SubGrid* defer = nullptr) {
+  using T = TileOf<ID>;
+  launch_gemm<T::BM, T::BN, T::BK, T::WM, T::WN, T::V>(p, s, wide_thr, sc, st, defer);
+}
 
-template <class P>
+// op OP on config c, which OP has an instantiation of (schedule.h effective_cfg)
+template <int OP, class P>
 inline void launch_cfg(int c, const P& p, int s, int wide_thr, const SplitScratch& sc,
                        hipStream_t st) {
-  if (c == CFG_KWAVE) {
-    if constexpr (KWaveOK<P>::value) {
-      launch_gemm_kwave<32>(p, s < 0 ? -s : s, st);
-      return;
-    }
-    c = 3;  // not instantiated for this op: the one-wave 32x32 tile
+  if constexpr (op_has_cfg(OP, CFG_KWAVE, true)) {
+    if (c == CFG_KWAVE) return launch_gemm_kwave<32>(p, s < 0 ? -s : s, st);
   }
-  if (c == CFG_KW16) {
-    if constexpr (KW16OK<P>::value) {
-      launch_gemm_kw16(p, s < 0 ? -s : s, st);
-      return;
-    }
-    c = 3;
+  if constexpr (op_has_cfg(OP, CFG_KW16, true)) {
+    if (c == CFG_KW16) return launch_gemm_kw16(p, s < 0 ? -s : s, st);
   }
-  if (c == CFG_MF16) {
-    if constexpr (Mf16OK<P>::value) {
-      launch_gemm<TILE_14>(p, s, wide_thr, sc, st);
-      return;
-    }
-    c = 3;
+  if constexpr (op_has_cfg(OP, CFG_MF16, true)) {
+    if (c == CFG_MF16) return launch_tile<CFG_MF16>(p, s, wide_thr, sc, st);
   }
   switch (c) {
-    case 0: launch_gemm<TILE_0>(p, s, wide_thr, sc, st); break;
-    case 1: launch_gemm<TILE_1>(p, s, wide_thr, sc, st); break;
-    case 2: launch_gemm<TILE_2>(p, s, wide_thr, sc, st); break;
-    case 3: launch_gemm<TILE_3>(p, s, wide_thr, sc, st); break;
-    case 4: launch_gemm<TILE_4>(p, s, wide_thr, sc, st); break;
-    case 5: launch_gemm<TILE_5>(p, s, wide_thr, sc, st); break;
-    case 6: launch_gemm<TILE_6>(p, s, wide_thr, sc, st); break;
-    case 7: launch_gemm<TILE_7>(p, s, wide_thr, sc, st); break;
-    default: launch_gemm<TILE_8>(p, s, wide_thr, sc, st); break;
+#define DDL_CASE(id, ...) \
+  case id: launch_tile<id>(p, s, wide_thr, sc, st); break;
+    TILE_TRAIN(DDL_CASE)
+#undef DDL_CASE
+    default: break;
   }
 }
 
@@ -125,57 +107,60 @@ inline auto make_policy(const Engine& e, int B, const float* x, const uint32_t* 
     return WgradConv1{M, N, K, x, e.d1, G[0], G[1]};
 }
 
+// schedule.h's support table against the traits the kernels are instantiated by (layers.h)
+template <int OP>
+using PolicyOf = decltype(make_policy<OP>(std::declval<const Engine&>(), 0, nullptr, nullptr, true));
+template <int... OP>
+constexpr bool tables_match_traits(std::integer_sequence<int, OP...>) {
+  return ((KWaveOK<PolicyOf<OP>>::value == op_has_cfg(OP, CFG_KWAVE, true) &&
+           Mf16OK<PolicyOf<OP>>::value == op_has_cfg(OP, CFG_MF16, true) &&
+           KW16OK<PolicyOf<OP>>::value == op_has_cfg(OP, CFG_KW16, true)) && ...);
+}
+static_assert(tables_match_traits(std::make_integer_sequence<int, OP_COUNT>{}),
+              "schedule.h kKWaveOps / kMf16Ops / kKw16Ops differ from layers.h's traits");
+
 template <int OP>
 void run_op_inst(Engine& e, const float* x, int B, const uint32_t* seed, bool train,
                      hipStream_t st, int si) {
+  const Schedule& s = e.sched;
   const auto p = make_policy<OP>(e, B, x, seed, train);
+  const int c = effective_cfg(OP, train ? s.cfg[OP] : s.eval_cfg[OP], train);
   if constexpr (OP == OP_CONV2_FWD) {
     // eval: conv2 on the tap-skipping K map (group-major rows), one-wave 64x64 tiles
-    if (!train && e.eval_kmap2 && e.eval_cfg[OP] == 0) {
+    if (!train && s.eval_kmap2 && c == 0) {
       const ConvFwd<14, 32, 64, true> pk{p.M, p.N, p.K, p.x, p.w, p.bias, p.out, p.code};
-      launch_gemm<TILE_0>(pk, 1, 1, e.scratch[si], st);
+      launch_tile<0>(pk, 1, 1, e.scratch[si], st);
       return;
     }
   }
-  if constexpr (OP == OP_CONV2_FWD || OP == OP_CONV3_FWD || OP == OP_CONV4_FWD) {
-    if (!train && e.eval_cfg[OP] >= NUM_TILE_CFGS) {  // eval-only large tiles, no split
-      switch (e.eval_cfg[OP]) {
-        case 9: launch_gemm<TILE_9>(p, 1, 1, e.scratch[si], st); break;
-        case 10: launch_gemm<TILE_10>(p, 1, 1, e.scratch[si], st); break;
-        case 11: launch_gemm<TILE_11>(p, 1, 1, e.scratch[si], st); break;
-        default: launch_gemm<TILE_12>(p, 1, 1, e.scratch[si], st); break;
+  if constexpr (op_has_cfg(OP, NUM_TILE_CFGS, false)) {
+    if (!train && c >= NUM_TILE_CFGS) {  // eval-only large tiles, no split
+      switch (c) {
+#define DDL_CASE(id, ...) \
+  case id: launch_tile<id>(p, 1, 1, e.scratch[si], st); break;
+        TILE_EVAL(DDL_CASE)
+#undef DDL_CASE
+        default: break;
       }
       return;
     }
   }
-  launch_cfg(train ? e.cfg[OP] : e.eval_cfg[OP], p, train ? e.splits[OP] : 1, e.wide[OP],
-             e.scratch[si], st);
+  launch_cfg<OP>(c, p, train ? s.splits[OP] : 1, s.wide[OP], e.scratch[si], st);
 }
 
 // ---- dual launches: data- and weight-gradient GEMM of one layer in one kernel -----------------
-// dual launches are instantiated for the one-wave configs: 32x32 (3), 32x32 BK 16 pipelined (5)
-// and the 16x16x4 tile (CFG_MF16) (the register-staged one-wave 64x64 / 32x64 tiles, 180-230
-// VGPRs, never won a dual launch in the real-step tuner)
-inline bool one_wave_cfg(int c) { return c == 3 || c == 5 || c == CFG_MF16; }
-
-template <int C> struct CfgOf;
-template <> struct CfgOf<3> { using T = TileCfg<TILE_3>; };
-template <> struct CfgOf<5> { using T = TileCfg<TILE_5>; };
-template <> struct CfgOf<CFG_MF16> { using T = TileCfg<TILE_14>; };
 template <int C> using IC = std::integral_constant<int, C>;
 
-// f(IC<c'>) for the one-wave config c' that op policy P runs for run-time config c (configs P
-// has no instantiation for fall back to 3; anything but 5 / MF16 likewise)
-template <class P, class F>
+// f(IC<c>) for the one-wave config c that op OP runs (schedule.h effective_cfg: 3, 5 or, for the
+// ops that have it, CFG_MF16)
+template <int OP, class F>
 inline void with_one_wave_cfg(int c, F&& f) {
-  if constexpr (Mf16OK<P>::value) {
+  if constexpr (op_has_cfg(OP, CFG_MF16, true)) {
     if (c == CFG_MF16) return f(IC<CFG_MF16>{});
   }
   if (c == 5) return f(IC<5>{});
   f(IC<3>{});
 }
-// every pairing of the one-wave configs is instantiated
-constexpr bool dual_pair_ok(int, int) { return true; }
 
 // The fc1 / fc2 weight gradients as extra blocks of the conv4 dual launch:
 // dW1 / dW2 feed only the optimizer, so they leave the fc backward's packed launches (which then
@@ -238,91 +223,57 @@ inline HeadWgradAux head_aux(Engine& e, int B) {
   return a;
 }
 
-template <int OA, int OB>
-inline void run_back_to_back(Engine& e, const float* x, int B, const uint32_t* seed,
-                             hipStream_t st) {
-  if constexpr (OA == OP_FC2_DGRAD || OA == OP_FC1_DGRAD) e.hit(BR_FC_BACK_TO_BACK);
-  else if constexpr (OA == OP_CONV4_DGRAD)  // (backward_segment flushes what is pending)
-    e.hit(e.fc_wgrad_pending ? BR_CONV4_BACK_TO_BACK_FLUSH : BR_CONV4_BACK_TO_BACK);
-  else if constexpr (OA == OP_CONV3_DGRAD) e.hit(BR_CONV3_BACK_TO_BACK);
-  else e.hit(BR_CONV2_BACK_TO_BACK);
-  e.flush_tail(st);
-  if constexpr (OA == OP_FC2_DGRAD) e.flush_head_wgrad(B, st);
-  run_op_inst<OA>(e, x, B, seed, true, st, 0);
-  run_op_inst<OB>(e, x, B, seed, true, st, 0);
-}
-
-template <class CA, class CB, int OA, int OB, class PA, class PB>
-inline void dual_b(Engine& e, const PA& pa, const PB& pb, int B, hipStream_t st) {
-  auto go = [&](const auto& aux) {
-    launch_gemm_dual<CA, PA, CB, PB>(pa, e.splits[OA], e.scratch[0], e.wide[OA], pb,
-                                     e.splits[OB], e.scratch[1], e.wide[OB], st, aux, nullptr,
-                                     e.dual_order(OA));
-  };
-  // the fc2 dual carries fc3's weight gradient; the conv4 dual the deferred fc weight
-  // gradients (if any) and the pending optimizer tail; the others the tail
-  if constexpr (OA == OP_FC2_DGRAD) {
-    e.hit(BR_FC_DUAL);
-    e.flush_tail(st);
-    go(head_aux(e, B));
-  } else if constexpr (OA == OP_CONV4_DGRAD) {
-    if (e.fc_wgrad_pending) {
-      e.hit(BR_CONV4_DUAL_FC_WGRAD);
-      go(fc_wgrad_aux(e, B, nullptr, nullptr));
-    } else {
-      e.hit(BR_CONV4_DUAL_TAIL);
-      go(TailAux(e.take_tail()));
-    }
-  } else {
-    e.hit(OA == OP_FC1_DGRAD ? BR_FC_DUAL
-                             : OA == OP_CONV3_DGRAD ? BR_CONV3_DUAL : BR_CONV2_DUAL);
-    go(TailAux(e.take_tail()));
-  }
-}
-
-// Ops OA and OB (independent) in one launch if both use one-wave tiles, else back to back.
-// OA on the K-wave config (fc data gradients) with OB on a one-wave 32x32 config: one packed
-// launch (gemm.h gemm_pack_kernel; OB's tiles run BK 32 there).
-// (fc only: the packed launch runs OB's tiles unsplit over the raw K range, which the conv weight
-// gradients' tap-window K maps do not support; a conv pair with a K-wave op runs back to back)
+// Ops OA and OB (independent) as schedule.h choose_pair says: one packed launch, one dual launch
+// or back to back.
 template <int OA, int OB>
 void run_dual_inst(Engine& e, const float* x, int B, const uint32_t* seed, hipStream_t st) {
-  constexpr bool fc_pair = OA == OP_FC2_DGRAD || OA == OP_FC1_DGRAD;
-  if (fc_pair && e.dual && e.cfg[OA] == CFG_KWAVE && (e.cfg[OB] == 3 || e.cfg[OB] == 5)) {
-    const auto pa = make_policy<OA>(e, B, x, seed, true);
-    auto pb = make_policy<OB>(e, B, x, seed, true);
-    if constexpr (fc_pair && KWaveOK<std::decay_t<decltype(pa)>>::value) {
-      // the weight gradient left to the conv4 dual launch (FcWgradAux): the pack carries the
-      // data gradient (and its aux work) only
-      if (e.fc_wgrad_defer) {
-        e.fc_wgrad_pending |= OA == OP_FC2_DGRAD ? 1 : 2;
-        pb.M = 0;
-      }
-      e.hit(e.fc_wgrad_defer ? BR_FC_PACK_DEFERRED : BR_FC_PACK_KEPT);
-      if constexpr (OA == OP_FC2_DGRAD) {
-        e.flush_tail(st);
-        launch_gemm_pack(pa, e.splits[OA], pb, head_aux(e, B), st);
-      } else {
-        launch_gemm_pack(pa, e.splits[OA], pb, TailAux(e.take_tail()), st);
-      }
-      return;
-    }
-  }
-  if (!e.dual || !one_wave_cfg(e.cfg[OA]) || !one_wave_cfg(e.cfg[OB])) {
-    run_back_to_back<OA, OB>(e, x, B, seed, st);
+  const Schedule& s = e.sched;
+  const PairChoice ch = choose_pair(s, OA, OB);
+  e.hit(pair_branch(OA, ch.kind, ch.defers, e.fc_wgrad_pending));
+  if (ch.kind == PAIR_BACK_TO_BACK) {
+    e.flush_tail(st);  // (backward_segment flushes the fc weight gradients that are pending)
+    if constexpr (OA == OP_FC2_DGRAD) e.flush_head_wgrad(B, st);
+    run_op_inst<OA>(e, x, B, seed, true, st, 0);
+    run_op_inst<OB>(e, x, B, seed, true, st, 0);
     return;
   }
   const auto pa = make_policy<OA>(e, B, x, seed, true);
-  const auto pb = make_policy<OB>(e, B, x, seed, true);
+  auto pb = make_policy<OB>(e, B, x, seed, true);
   using PA = std::decay_t<decltype(pa)>;
   using PB = std::decay_t<decltype(pb)>;
-  with_one_wave_cfg<PA>(e.cfg[OA], [&](auto ca) {
-    with_one_wave_cfg<PB>(e.cfg[OB], [&](auto cb) {
-      constexpr int A = decltype(ca)::value, Bc = decltype(cb)::value;
-      if constexpr (dual_pair_ok(A, Bc))
-        dual_b<typename CfgOf<A>::T, typename CfgOf<Bc>::T, OA, OB>(e, pa, pb, B, st);
-      else
-        run_back_to_back<OA, OB>(e, x, B, seed, st);
+  // go(the launch's aux blocks): fc2's launch carries fc3's weight gradient (the pending tail is
+  // flushed: schedule.h pair_takes_tail, a pack's as a dual's); the conv4 dual the deferred fc
+  // weight gradients (if any) and the pending optimizer tail; the others the tail
+  auto with_aux = [&](auto&& go) {
+    if constexpr (!pair_takes_tail(OA, PAIR_DUAL)) {
+      e.flush_tail(st);
+      go(head_aux(e, B));
+    } else {
+      if constexpr (OA == OP_CONV4_DGRAD) {
+        if (e.fc_wgrad_pending) return go(fc_wgrad_aux(e, B, nullptr, nullptr));
+      }
+      go(TailAux(e.take_tail()));
+    }
+  };
+  if (ch.kind == PAIR_PACK) {
+    if constexpr (is_fc_pair(OA)) {
+      // the weight gradient left to the conv4 dual launch (FcWgradAux): the pack carries the
+      // data gradient (and its aux work) only
+      if (ch.defers) {
+        e.fc_wgrad_pending |= OA == OP_FC2_DGRAD ? 1 : 2;
+        pb.M = 0;
+      }
+      with_aux([&](const auto& aux) { launch_gemm_pack(pa, s.splits[OA], pb, aux, st); });
+    }
+    return;
+  }
+  with_one_wave_cfg<OA>(ch.ca, [&](auto ca) {
+    with_one_wave_cfg<OB>(ch.cb, [&](auto cb) {
+      with_aux([&](const auto& aux) {
+        launch_gemm_dual<TileOf<decltype(ca)::value>, PA, TileOf<decltype(cb)::value>, PB>(
+            pa, s.splits[OA], e.scratch[0], s.wide[OA], pb, s.splits[OB], e.scratch[1],
+            s.wide[OB], st, aux, nullptr, s.dual_order(OA));
+      });
     });
   });
 }
@@ -440,8 +391,7 @@ inline bool final_split_conv12(const Engine& e, const UpdTail& in, const PB& pb,
 
 // Dual launch OA + OB, then op ON with OB's wide split-K reduce fused into ON's launch (both
 // need only what the dual wrote; saves one dependent boundary: conv2 dual -> [conv2 wgrad
-// reduce | conv1 wgrad GEMM]).  Instantiated for the tuned configs (OA: 32x32, OB: 32x32
-// BK 16 pipelined, ON: 32x32 split-K); any other schedule takes the unfused sequence.
+// reduce | conv1 wgrad GEMM]).  Instantiated for the schedules schedule.h choose_seg3 fuses.
 template <int OA, int OB, int ON, class CA, class CB>
 void dual_then_b(Engine& e, const float* x, int B, const uint32_t* seed, hipStream_t st) {
   const auto pa = make_policy<OA>(e, B, x, seed, true);
@@ -450,18 +400,19 @@ void dual_then_b(Engine& e, const float* x, int B, const uint32_t* seed, hipStre
   using PA = std::decay_t<decltype(pa)>;
   using PB = std::decay_t<decltype(pb)>;
   using PN = std::decay_t<decltype(pn)>;
-  using CN = TileCfg<TILE_3>;
+  using CN = TileOf<3>;
+  const Schedule& s = e.sched;
   SubGrid gb;
-  launch_gemm_dual<CA, PA, CB, PB>(pa, e.splits[OA], e.scratch[0], e.wide[OA], pb,
-                                   e.splits[OB], e.scratch[1], e.wide[OB], st,
-                                   TailAux(e.take_tail()), &gb, e.dual_order(OA));
+  launch_gemm_dual<CA, PA, CB, PB>(pa, s.splits[OA], e.scratch[0], s.wide[OA], pb,
+                                   s.splits[OB], e.scratch[1], s.wide[OB], st,
+                                   TailAux(e.take_tail()), &gb, s.dual_order(OA));
   constexpr bool kFinal = ON == OP_CONV1_WGRAD;
   if constexpr (kFinal) {
     // conv1's weight gradient on the direct kernel (conv1.h), sharing its launch with OB's
     // pending reduce; scratch[0] is free here (OA's split-K finished inside the dual launch
     // or in its own reduce before this point)
     const bool direct =
-        e.conv1_wgrad_direct && conv1_wgrad_direct_ok(B, e.slab_floats, e.scratch[0].max_tiles);
+        s.conv1_wgrad_direct && conv1_wgrad_direct_ok(B, e.slab_floats, e.scratch[0].max_tiles);
     if (direct) {
       e.hit(gb.mode == 2 ? BR_SEG3_DIRECT_REDUCE : BR_SEG3_DIRECT);
       float* part = static_cast<float*>(e.scratch[0].slab);
@@ -484,7 +435,7 @@ void dual_then_b(Engine& e, const float* x, int B, const uint32_t* seed, hipStre
   }
   const bool fin = kFinal && e.final_upd.npieces > 0;
   SubGrid gn;
-  if (!launch_reduce_with_gemm<CB, PB, CN, PN>(pb, gb, pn, e.splits[ON], e.wide[ON],
+  if (!launch_reduce_with_gemm<CB, PB, CN, PN>(pb, gb, pn, s.splits[ON], s.wide[ON],
                                                e.scratch[0], st,
                                                fin ? &gn : nullptr)) {
     e.hit(BR_SEG3_REDUCE_REFUSED);
@@ -508,30 +459,21 @@ void dual_then_b(Engine& e, const float* x, int B, const uint32_t* seed, hipStre
   }
 }
 
-// Instantiated for OA / OB on the one-wave configs (dual_pair_ok), ON on 32x32 split-K; any
-// other schedule takes the unfused sequence.
+// Segment 3 as schedule.h choose_seg3 says: fused, or the pair and then ON.
 template <int OA, int OB, int ON>
 void run_dual_then_inst(Engine& e, const float* x, int B, const uint32_t* seed, hipStream_t st) {
-  const int ca = e.cfg[OA], cb = e.cfg[OB];
-  if (!e.dual || (ca != 3 && ca != CFG_MF16) || (cb != 3 && cb != 5 && cb != CFG_MF16) ||
-      e.cfg[ON] != 3) {
+  const Seg3Choice ch = choose_seg3(e.sched);
+  if (!ch.fused) {
     e.hit(BR_SEG3_UNFUSED);
     run_dual_inst<OA, OB>(e, x, B, seed, st);
     e.run_op(ON, x, B, seed, true, st, 0);
     return;
   }
-  using PA = decltype(make_policy<OA>(e, B, x, seed, true));
-  using PB = decltype(make_policy<OB>(e, B, x, seed, true));
-  with_one_wave_cfg<PA>(ca, [&](auto ia) {
-    with_one_wave_cfg<PB>(cb, [&](auto ib) {
+  with_one_wave_cfg<OA>(ch.ca, [&](auto ia) {
+    with_one_wave_cfg<OB>(ch.cb, [&](auto ib) {
       constexpr int A = decltype(ia)::value, Bc = decltype(ib)::value;
-      if constexpr (A != 5 && dual_pair_ok(A, Bc)) {
-        dual_then_b<OA, OB, ON, typename CfgOf<A>::T, typename CfgOf<Bc>::T>(e, x, B, seed, st);
-      } else {
-        e.hit(BR_SEG3_UNFUSED);
-        run_dual_inst<OA, OB>(e, x, B, seed, st);
-        e.run_op(ON, x, B, seed, true, st, 0);
-      }
+      if constexpr (A != 5)  // (never chosen: not instantiated)
+        dual_then_b<OA, OB, ON, TileOf<A>, TileOf<Bc>>(e, x, B, seed, st);
     });
   });
 }

@@ -174,11 +174,9 @@ SyncRunner::SyncRunner(Engine* eng, float* params, float* grads, int world, int 
   HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&ready_err_), 64, hipHostMallocDefault));
   memset(ready_err_, 0, 64);
   HIP_CHECK(hipDeviceSynchronize());
-  const char* xe = getenv("DDL_EXT_EVENT");
-  ext_event_ = xe ? xe[0] == '1' : true;
+  ext_event_ = env_flag("DDL_EXT_EVENT", true, /*only_1=*/true);
   // the READY gate is bounded like the xGMI waits (the same setting and default)
-  const char* to = getenv("DDL_XGMI_TIMEOUT_S");
-  gate_timeout_s_ = to ? atof(to) : 20.0;
+  gate_timeout_s_ = xgmi_timeout_s(20.0);
 }
 
 SyncRunner::~SyncRunner() {

@@ -472,8 +472,7 @@ struct HandleBlob {  // what one rank publishes (exchanged as bytes over the def
 
 PeerMap::PeerMap(const char* tag, float* params, int world, int rank, double default_timeout_s)
     : tag_(tag), params_(params), world_(world), rank_(rank) {
-  const char* t = getenv("DDL_XGMI_TIMEOUT_S");
-  timeout_s = t ? atof(t) : default_timeout_s;  // a healthy wait takes microseconds
+  timeout_s = xgmi_timeout_s(default_timeout_s);  // a healthy wait takes microseconds
 }
 
 void PeerMap::alloc(int64_t inbox_elems, size_t flag_bytes) {
@@ -663,8 +662,7 @@ void PeerExchange::init(const std::vector<XgmiBucketSpec>& buckets, int max_slic
   // ARRIVE, DONE and (check mode) checksum words, the replicated bucket's in two parities
   map_.alloc(inbox, 4ull * kXgmiMaxBuckets * kXgmiMaxPeers * kXgmiMaxSlices * sizeof(uint32_t));
   X_CHECK(hipDeviceSynchronize());
-  const char* ck = getenv("DDL_XGMI_CHECK");
-  check_ = ck && ck[0] == '1';
+  check_ = env_flag("DDL_XGMI_CHECK", false, /*only_1=*/true);
 }
 
 PeerExchange::~PeerExchange() { close(); }

@@ -1,7 +1,8 @@
 """HIP engine: the CNN step on hand-written gfx950 kernels, replayed as HIP graphs.
 
 The C++ ``Engine`` (``csrc/kernels/engine.hip``) owns all activation / gradient-scratch
-buffers and launches every kernel of a step on torch's current stream.  This wrapper:
+buffers and launches every kernel of a step on torch's current stream, as its launch schedule
+(``csrc/kernels/schedule.h``) says.  This wrapper:
 
 * binds the 14 parameter / gradient views of the plan-ordered flat buffers (so the
   exchange layer can slice PS shards straight out of them);
@@ -10,7 +11,8 @@ buffers and launches every kernel of a step on torch's current stream.  This wra
 * captures the forward + backward as **four HIP graphs**, one per backward segment
   (fc head, conv4, conv3, conv2+conv1); between replays it calls ``on_segment(s)`` so
   the sync exchange can push that segment's gradients on a side stream while the next
-  graph computes.  A replay costs one host call instead of ~25 kernel launches.
+  graph computes.  A replay costs one host call per segment instead of the step's 16 kernel
+  launches (single stream, each layer's two gradient GEMMs in one dual or packed launch).
 """
 from __future__ import annotations
 

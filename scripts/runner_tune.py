@@ -15,13 +15,10 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-# engine op order (csrc/kernels/api.h enum Op)
+# engine op order (csrc/kernels/schedule.h enum Op)
 OPS = ["conv1_fwd", "conv2_fwd", "conv3_fwd", "conv4_fwd", "fc1_fwd", "fc2_fwd",
        "fc2_dgrad", "fc2_wgrad", "fc1_dgrad", "fc1_wgrad", "conv4_dgrad", "conv4_wgrad",
        "conv3_dgrad", "conv3_wgrad", "conv2_dgrad", "conv2_wgrad", "conv1_wgrad"]
-
-KWAVE_OK = {4, 5, 6, 8}  # fc forward / data-gradient GEMMs (csrc/kernels/layers.h KWaveOK)
-MF16_OK = {1, 2, 3, 10, 11, 12, 13, 14, 15}  # conv GEMMs with 16-byte gathers (layers.h Mf16OK)
 
 
 def main():
@@ -52,11 +49,16 @@ def main():
     W = 1 << 20
     cur = {"cfg": e.get_cfg(), "splits": e.get_splits(), "wide": e.get_wide()}
     step = [0]
+    rows = []   # every candidate timed: its config, the config that ran, its time
 
     def apply(s):
         e.set_cfg(s["cfg"])
         e.set_splits(s["splits"])
         e.set_wide(s["wide"])
+
+    def effective(s):  # the configs that really run under s (schedule.h effective_cfg)
+        apply(s)
+        return list(e.effective_cfg())
 
     def timed(s):
         apply(s)
@@ -84,14 +86,15 @@ def main():
                           max(1, (3 * s) // 4), min(2048, (3 * s) // 2)} - {s}):
             out.append(mk(c, s2, 0, wd))
         out.append(mk(c, s, 0, 1 if wd > 1 else W))            # toggle the reduce mode
-        for c2 in (0, 3, 4, 5):  # the one-wave configs (dual launches instantiate these)
+        # one-wave configs (only 3, 5 and 14 have dual launches: 0 or 4 runs a pair back to back)
+        for c2 in (0, 3, 4, 5):
             if c2 != c:
                 out.append(mk(c2, s, 0, wd))
-        if op in MF16_OK:  # CFG_MF16 (16x16x4 MFMA, LDS-DMA), at the split and twice it
+        if e.op_has_cfg(op, 14, True):  # CFG_MF16 (16x16x4 MFMA, LDS-DMA), at the split and twice it
             for s2 in sorted({s, min(2048, s * 2)}):
                 if (c, s) != (14, s2):
                     out.append(mk(14, s2, 0, wd))
-        if op in MF16_OK and a.dma:  # (configs 16-20 were removed in round 6)
+        if e.op_has_cfg(op, 14, True) and a.dma:  # (configs 16-20 were removed in round 6)
             for s2 in sorted({min(2048, s * 4), max(1, s // 2)}):
                 if (c, s) != (14, s2):
                     out.append(mk(14, s2, 0, wd))
@@ -99,7 +102,7 @@ def main():
             for c2 in (1, 2, 6, 7, 8):
                 for s2 in sorted({s, min(2048, s * 2), max(1, s // 2)}):
                     out.append(mk(c2, s2, 0, wd))
-        if op in KWAVE_OK:  # K split over the waves of one workgroup (4 / 8 / 16 waves)
+        if e.op_has_cfg(op, 13, True):  # K split over the waves of one workgroup (4 / 8 / 16 waves)
             for s2 in (4, 8, 16):
                 if (c, s) != (13, s2):
                     out.append(mk(13, s2, 0, wd))
@@ -114,10 +117,12 @@ def main():
             best, best_t = None, None
             for cand in cands(op):
                 t = timed(cand)
+                row = dict(op=name, cfg=cand["cfg"][op], effective_cfg=effective(cand)[op],
+                           splits=cand["splits"][op], inl=cand["wide"][op] > 1, us=t)
+                rows.append(row)
                 if a.verbose:
-                    print(f"    {name:12s} c{cand['cfg'][op]} s{cand['splits'][op]} "
-                          f"{'inl' if cand['wide'][op] > 1 else 'wide'} "
-                          f"{t:.1f}", flush=True)
+                    print(f"    {name:12s} c{row['cfg']} (runs c{row['effective_cfg']}) "
+                          f"s{row['splits']} {'inl' if row['inl'] else 'wide'} {t:.1f}", flush=True)
                 if best_t is None or t < best_t:
                     best, best_t = cand, t
             # head-to-head re-measure of the incumbent vs the best candidate
@@ -125,7 +130,8 @@ def main():
             t_new = min(timed(best), timed(best))
             if t_new < t_inc * (1 - a.gain):
                 cur = best
-                print(f"pass {p} {name:12s} -> c{cur['cfg'][op]} s{cur['splits'][op]} "
+                print(f"pass {p} {name:12s} -> c{cur['cfg'][op]} (runs c{effective(cur)[op]}) "
+                      f"s{cur['splits'][op]} "
                       f"{'inl' if cur['wide'][op] > 1 else 'wide'}  "
                       f"{t_inc:.1f} -> {t_new:.1f} us", flush=True)
             else:
@@ -136,7 +142,8 @@ def main():
     print("DEFAULT_SPLITS", ",".join(map(str, cur["splits"])))
     print("DEFAULT_INL", ",".join("1" if w > 1 else "0" for w in cur["wide"]))
     if a.json:
-        json.dump(dict(cur, step_us=final, start_us=base), open(a.json, "w"), indent=1)
+        json.dump(dict(cur, effective_cfg=effective(cur), step_us=final, start_us=base,
+                       candidates=rows), open(a.json, "w"), indent=1)
 
 
 if __name__ == "__main__":

@@ -7,15 +7,16 @@ A schedule is a dict of what differs from the engine's defaults:
 * ``dual``, ``bfirst`` (ops whose layer dispatches its second problem first), ``direct`` (both
   conv1 switches), ``concurrent``, ``defer`` (`set_fc_wgrad_defer`).
 
-`expected_hits` is the host dispatch of engine.hip `backward_segment` and engine_impl.h
-`run_dual_inst` / `run_dual_then_inst` / `dual_then_b` written down once more, as
+`expected_hits` is the host dispatch of engine.hip `backward_segment`, schedule.h `choose_pair` /
+`choose_seg3` / `pair_branch` and engine_impl.h `dual_then_b` written down once more, as
 step_audit.expected_update_launches writes down the runners': the GPU test demands that
 `dispatch_hits()` after a segment equals it exactly, every other counter 0.
-tests/test_dispatch_cells_cpu.py holds the table against BRANCHES.
+tests/test_dispatch_cells_cpu.py holds the table against BRANCHES and, without a GPU, against
+schedule.h itself (csrc/kernels/tests/schedule_check.cpp).
 """
 import itertools
 
-# csrc/kernels/api.h enum Branch, in its order (the GPU test holds it against dispatch_hits())
+# csrc/kernels/schedule.h enum Branch, in its order (the GPU test holds it against dispatch_hits())
 BRANCHES = [
     "fc_pack_deferred", "fc_pack_kept", "fc_dual", "fc_back_to_back",
     "conv4_dual_fc_wgrad", "conv4_dual_tail", "conv4_back_to_back_flush", "conv4_back_to_back",
@@ -24,7 +25,7 @@ BRANCHES = [
     "seg3_unfused", "tail_standalone", "tail_consumed", "concurrent",
 ]
 
-# csrc/kernels/api.h enum Op and the engine's defaults (engine.hip Engine::Engine)
+# csrc/kernels/schedule.h enum Op and the engine's defaults (Schedule::defaults)
 FC2_DGRAD, FC2_WGRAD, FC1_DGRAD, FC1_WGRAD = 6, 7, 8, 9
 CONV4_DGRAD, CONV4_WGRAD, CONV3_DGRAD, CONV3_WGRAD = 10, 11, 12, 13
 CONV2_DGRAD, CONV2_WGRAD, CONV1_WGRAD = 14, 15, 16
@@ -36,6 +37,12 @@ WIDE_INLAUNCH, WIDE_SEPARATE = 1 << 20, 1
 DEF_WIDE = [WIDE_INLAUNCH if i else WIDE_SEPARATE for i in DEF_INLAUNCH]
 DEF_BFIRST = (CONV2_DGRAD, CONV3_DGRAD)
 ONE_WAVE = (3, 5, MF16)
+# ops with an instantiation of the K-wave launch (13), the 16x16x4 tile (14) and the 16-row K-wave
+# launch (15): csrc/kernels/schedule.h op_has_cfg (tests/test_dispatch_cells_cpu.py holds them
+# against it); every other op falls back to config 3
+KWAVE_OPS = (4, 5, 6, 8)
+MF16_OPS = (1, 2, 3, 10, 11, 12, 13, 14, 15)
+KW16_OPS = (4, 5)
 # segment -> (data-gradient op, weight-gradient op) of its conv layer
 PAIR = {1: (CONV4_DGRAD, CONV4_WGRAD), 2: (CONV3_DGRAD, CONV3_WGRAD), 3: (CONV2_DGRAD, CONV2_WGRAD)}
 LAYER = {1: "conv4", 2: "conv3", 3: "conv2"}

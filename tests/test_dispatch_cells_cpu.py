@@ -1,6 +1,14 @@
 """The cell table of tests/test_dispatch_oracle_gpu.py (tests/dispatch_cells.py), without a GPU:
 every cell names at least one branch and only known ones, and every branch name is expected by
-some cell (the GPU test holds BRANCHES against the engine's own dispatch_hits().keys())."""
+some cell (the GPU test holds BRANCHES against the engine's own dispatch_hits().keys()); and the
+table's defaults, config support and expected branches equal those of csrc/kernels/schedule.h,
+run as a stand-alone host program."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
 import dispatch_cells as D
 
 
@@ -43,3 +51,137 @@ def test_split_counts_follow_gemm_h():
     assert D.splitk_z(6272, 48, 32) == 40 and D.splitk_z(6272, 12, 16) == 12
     assert D.mode_of(6272, 48, 1, 32) == 2 and D.mode_of(6272, 48, 1 << 20, 32) == 1
     assert D.mode_of(6272, 1, 1, 32) == 0
+
+
+# ---- the twin against csrc/kernels/schedule.h ------------------------------------------------------
+FUSED = ("seg3_direct_reduce", "seg3_direct", "seg3_reduce_gemm", "seg3_reduce_refused")
+
+
+def cell_line(sched, walk):
+    """One input line of schedule_check.cpp: the schedule's differences from the defaults, then
+    the (segment, tail pending) steps."""
+    out = ["cell"]
+    for k in ("cfg", "splits", "wide"):
+        for op, v in sched.get(k, {}).items():
+            out += [k, op, v]
+    for key, name in (("dual", "dual"), ("direct", "direct"), ("concurrent", "concurrent"),
+                      ("defer", "defer")):
+        if key in sched:
+            out += [name, int(sched[key])]
+    if "bfirst" in sched:
+        out += ["bfirst", sum(1 << op for op in sched["bfirst"])]
+    for s, tail in walk:
+        out += ["seg", s, int(tail)]
+    return " ".join(map(str, out))
+
+
+def hits_text(h, pend):
+    """expected_hits' counters as the program prints them: enum order, the four fused outcomes of
+    segment 3 (known only once the launch is planned) as one name."""
+    fused = sum(h.get(b, 0) for b in FUSED)
+    out = [f"{b}={h[b]}" for b in D.BRANCHES if b in h and b not in FUSED]
+    if fused:
+        out.append(f"seg3_fused={fused}")
+    return " ".join(out) + f" pend {int(bool(pend))}"
+
+
+def twin_cells(K15=6272):
+    """(name, input line, expected text) of every cell of all_expectations(), in its order."""
+    out = []
+    for s in (1, 2, 3):
+        for name, sched in D.segment_cells(s):
+            out.append((name, cell_line(sched, [(s, False)]),
+                        hits_text(*D.expected_hits(s, sched, K15))))
+    for s, name, sched in D.TAIL_CELLS:
+        out.append(("tail: " + name, cell_line(sched, [(s, True)]),
+                    hits_text(*D.expected_hits(s, sched, K15, tail=True))))
+    for name, c in D.CHAIN_CELLS.items():
+        for label, tails in (("chain: ", False), ("chain + tails: ", True)):
+            h0, pend = D.expected_hits(0, c["sched"], tail=tails)
+            _, pend = D.expected_hits(1, c["sched"], tail=tails, fc_pending=pend)
+            out.append((label + name, cell_line(c["sched"], [(0, tails), (1, tails)]),
+                        hits_text(D.chain_expected(c["sched"], tails, tails), pend)))
+    return out
+
+
+@pytest.fixture(scope="module")
+def schedule_check(tmp_path_factory):
+    """csrc/kernels/tests/schedule_check.cpp built with AddressSanitizer +
+    UndefinedBehaviorSanitizer (hipcc's host compiler, else g++) and run on every cell: its output
+    lines by their first word."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = os.path.join(root, "distributed-deep-learning_amd", "csrc", "kernels", "tests",
+                       "schedule_check.cpp")
+    hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
+    exe = str(tmp_path_factory.mktemp("schedule_check") / "schedule_check")
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+    if os.path.exists(hipcc):
+        cmd = [hipcc, "--offload-arch=gfx950", "-std=c++17", "-O1", "-g",
+               *[a for f in san for a in ("-Xarch_host", f)], src, "-o", exe]
+    elif shutil.which("g++"):
+        cmd = ["g++", "-std=c++17", "-O1", "-g", *san, src, "-o", exe]
+    else:
+        pytest.skip("needs hipcc or g++")
+    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    text = "".join(line + "\n" for _, line, _ in twin_cells())
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
+               UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr
+    out = {}
+    for line in r.stdout.splitlines():
+        out.setdefault(line.split()[0], []).append(line.split()[1:])
+    return out
+
+
+def test_defaults_equal_schedule_h(schedule_check):
+    rows = {r[0]: r[1:] for r in schedule_check["defaults"]}
+    assert [int(v) for v in rows["cfg"]] == D.DEF_CFG
+    assert [int(v) for v in rows["splits"]] == D.DEF_SPLITS
+    assert [int(v) for v in rows["wide"]] == D.DEF_WIDE
+    flags = dict(kv.split("=") for kv in rows["flags"])
+    assert int(flags["bfirst"]) == sum(1 << op for op in D.DEF_BFIRST)
+    # what resolved() takes for a schedule that names none of them
+    assert (flags["dual"], flags["concurrent"], flags["fc_wgrad_defer"]) == ("1", "0", "1")
+    assert (flags["conv1_direct"], flags["conv1_wgrad_direct"]) == ("1", "1")
+
+
+def test_config_support_equals_schedule_h(schedule_check):
+    (cfgs,) = schedule_check["configs"]
+    assert cfgs[:3] == [f"kwave={D.KWAVE}", f"mf16={D.MF16}", "kw16=15"]
+    assert cfgs[3] == "one_wave" and tuple(int(c) for c in cfgs[4:]) == D.ONE_WAVE
+    has, eff = {}, {}
+    for op, cfg, train, h, e in (map(int, r) for r in schedule_check["support"]):
+        has[op, cfg, train], eff[op, cfg, train] = h, e
+    assert len(has) == 17 * 16 * 2
+    want = {D.KWAVE: D.KWAVE_OPS, D.MF16: D.MF16_OPS, 15: D.KW16_OPS}
+    for (op, cfg, train), h in has.items():
+        if cfg < 9:
+            assert h == 1
+        elif cfg < 13:   # the eval-only large tiles: conv2-4 forward, train = false
+            assert h == (not train and op in (1, 2, 3))
+        else:
+            assert h == (op in want[cfg]), (op, cfg, train)
+        # what runs: the config itself, else the one-wave 32x32 tile; conv2-4's eval forward runs
+        # every config past the training tiles on its large-tile switch (default: tile 12)
+        if not train and op in (1, 2, 3) and cfg >= 13:
+            assert eff[op, cfg, train] == 12
+        else:
+            assert eff[op, cfg, train] == (cfg if h else 3), (op, cfg, train)
+
+
+def test_every_cell_matches_schedule_h(schedule_check):
+    cells = twin_cells()
+    assert [name for name, _, _ in cells] == [name for name, _ in D.all_expectations()]
+    got = schedule_check["cell"]
+    assert len(got) == len(cells)
+    choices = set()
+    tails = set()
+    for i, ((name, line, want), g) in enumerate(zip(cells, got)):
+        assert g[0] == str(i) and g[1] == "choices" and g[3] == "hits", name
+        assert " ".join(g[4:]) == want, (name, line)
+        choices |= set(g[2].split(","))
+        tails |= {t.split("=")[0] for t in g[4:] if t.startswith("tail_")}
+    # all three kinds of PairChoice, both values of Seg3Choice, both tail dispositions
+    assert choices == {"pack", "dual", "back_to_back", "fused", "unfused", "concurrent"}
+    assert tails == {"tail_consumed", "tail_standalone"}

@@ -348,8 +348,23 @@ def test_kwave_config_matches_reference(setup, waves, packed):
         eng.set_splits(base_s)
 
 
-# conv2-4 forward, conv4..conv2 data / weight gradient (csrc/kernels/api.h op order)
+# conv2-4 forward, conv4..conv2 data / weight gradient (csrc/kernels/schedule.h op order)
 MF16_OPS = (1, 2, 3, 10, 11, 12, 13, 14, 15)
+KWAVE_OPS = (4, 5, 6, 8)   # fc forwards and data gradients (test_kwave_config_matches_reference)
+KW16_OPS = (4, 5)          # fc forwards (test_kw16_fc_matches_reference)
+
+
+def test_special_config_op_sets_are_the_engines(setup):
+    """The op sets these tests put on configs 13 / 14 / 15 are the ops the engine has those
+    instantiations for (Engine.op_has_cfg, csrc/kernels/schedule.h): a config anywhere else falls
+    back to config 3, silently, and such a test would pass without running its kernel."""
+    eng = setup[0].eng
+    for cfg, ops in ((13, KWAVE_OPS), (14, MF16_OPS), (15, KW16_OPS)):
+        for train in (True, False):
+            assert tuple(op for op in range(17) if eng.op_has_cfg(op, cfg, train)) == ops
+    cfg = list(eng.get_cfg())
+    assert eng.effective_cfg() == [c if eng.op_has_cfg(op, c, True) else 3
+                                   for op, c in enumerate(cfg)]
 
 
 @pytest.mark.parametrize("mode", ["default", "split1", "wide", "nodual", "mixed"])

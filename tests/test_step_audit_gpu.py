@@ -118,7 +118,7 @@ def _fc2_split(tr):
 
 
 def _schedule(cfg=None, wide=None):
-    """Tile configs / wide thresholds by op (csrc/kernels/api.h enum Op) over the defaults."""
+    """Tile configs / wide thresholds by op (csrc/kernels/schedule.h enum Op) over the defaults."""
     def setup(tr):
         e = tr.engine.eng
         if cfg:
