@@ -26,9 +26,59 @@ void check_f32_cuda(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
 
+// The optimizer of a Python call as an OptimSpec (kernels/ps_bank.h), in true doubles or with lr,
+// b1 and b2 rounded to float32 first (`f32`); its refusals as torch errors under `tag`.  The
+// decay is upd_decay(lr, weight_decay): rounded to float here, once.
+ddl::OptimSpec spec_of(const char* tag, int64_t kind, double lr, double b1, double b2, double eps,
+                       double mu, double scale, double weight_decay, bool nesterov,
+                       bool f32 = false) {
+  try {
+    const float e = (float)eps, m = (float)mu, s = (float)scale;
+    const float decay = ddl::upd_decay(lr, weight_decay);
+    return f32 ? ddl::OptimSpec::from_float32((int)kind, lr, b1, b2, e, m, s, decay, nesterov)
+               : ddl::OptimSpec::from_doubles((int)kind, lr, b1, b2, e, m, s, decay, nesterov);
+  } catch (const std::invalid_argument& e) {
+    TORCH_CHECK(false, tag, ": ", e.what());
+  }
+}
+// The rule alone where the call carries its step size and its decay lr * wd ready-made (a double:
+// the product with 1 is exact, so upd_decay rounds it as it stands)
+ddl::UpdRule rule_of(int64_t kind, double b1, double b2, double eps, double mu, double scale,
+                     double decay, bool nesterov) {
+  return spec_of("update", kind, 1.0, b1, b2, eps, mu, scale, decay, nesterov).rule;
+}
+
+// [(ps id, params, m, v | None, t)] as hosted PS states; the tensors go to `keep`
+std::vector<ddl::AsyncPsState> ps_states(py::list ps, std::vector<at::Tensor>& keep,
+                                         bool need_v = false) {
+  std::vector<ddl::AsyncPsState> st;
+  auto ptr = [&](py::handle h, const char* name) {
+    at::Tensor x = h.cast<at::Tensor>();
+    check_f32_cuda(x, name);
+    keep.push_back(x);
+    return x.data_ptr<float>();
+  };
+  for (auto item : ps) {
+    auto t = item.cast<py::tuple>();
+    TORCH_CHECK(!need_v || !t[3].is_none(), "in-line applies are Adam: v required");
+    st.push_back({t[0].cast<int>(), ptr(t[1], "ps params"), ptr(t[2], "m"),
+                  t[3].is_none() ? nullptr : ptr(t[3], "v"), t[4].cast<int64_t>()});
+  }
+  return st;
+}
+// [(lo, hi)] element ranges
+std::vector<std::pair<int64_t, int64_t>> index_ranges(py::list ranges) {
+  std::vector<std::pair<int64_t, int64_t>> rg;
+  for (auto r : ranges) {
+    auto t = r.cast<py::tuple>();
+    rg.emplace_back(t[0].cast<int64_t>(), t[1].cast<int64_t>());
+  }
+  return rg;
+}
+
 // One update of a flat span under rule `kind` of update.h (copy: m and v may be None; momentum:
 // v may be).  The step size rides beside it: Adam's lr_t, or the learning rate.  `decay` is the
-// decoupled weight decay's lr * wd, as a double: rounded to float here, once (update.h upd_decay).
+// decoupled weight decay's lr * wd, as a double.
 struct FlatUpdate {
   ddl::UpdRule rule;
   ddl::UpdSpan span;
@@ -37,12 +87,7 @@ struct FlatUpdate {
   FlatUpdate(int64_t kind, at::Tensor w, at::Tensor gt, c10::optional<at::Tensor> m,
              c10::optional<at::Tensor> v, double b1, double b2, double eps, double mu,
              double scale, double decay = 0.0, bool nesterov = false)
-      : rule((int)kind, (float)b1, (float)b2, (float)eps, (float)mu, (float)scale, (float)decay,
-             nesterov),
-        n(w.numel()) {
-    TORCH_CHECK(kind >= 0 && kind <= 2, "update: rule kind");
-    TORCH_CHECK(decay >= 0.0, "update: negative weight decay");
-    TORCH_CHECK(!nesterov || kind == ddl::kUpdMomentum, "update: Nesterov needs the momentum rule");
+      : rule(rule_of(kind, b1, b2, eps, mu, scale, decay, nesterov)), n(w.numel()) {
     TORCH_CHECK((m || kind == ddl::kUpdCopy) && (v || kind != ddl::kUpdAdam),
                 "update: optimizer state missing");
     auto ptr = [&](const at::Tensor& t, const char* name) {
@@ -388,7 +433,18 @@ class PyEngine {
 
   int64_t max_batch() const { return e_.max_batch; }
   ddl::Engine* raw() { return &e_; }
-  void check_batch(const at::Tensor& x) { check_x(x); }
+  // a runner's micro-batch, checked: the pointers and B
+  struct Batch {
+    const float* x;
+    const int64_t* labels;
+    int B;
+  };
+  Batch batch(const at::Tensor& x, const at::Tensor& labels) {
+    check_x(x);
+    TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_cuda(), "labels must be int64 GPU");
+    TORCH_CHECK(labels.numel() == x.size(0), "labels/batch size mismatch");
+    return {x.data_ptr<float>(), labels.data_ptr<int64_t>(), (int)x.size(0)};
+  }
   int64_t workspace_bytes() const { return (int64_t)e_.workspace_bytes(); }
   static std::vector<int64_t> op_shape(int64_t op, int64_t B) {
     int M, N, K;
@@ -422,16 +478,49 @@ class PyEngine {
   at::Device device_{at::kCPU};
 };
 
-// Python-facing wrapper of ddl::SyncRunner (native sync step: engine + exchange + update).
-// xGMI peer exchange (kernels/xgmi.hip): IPC handles out, every rank's handles in.
-class PyPeer {
+// What the wrappers of the two xGMI exchanges P (PeerExchange, AsyncPeer) share: the buffers and
+// the IPC life cycle (handles out, every rank's handles in), each call on the parameters' device.
+template <class P>
+class PyPeerBase {
  public:
-  PyPeer(at::Tensor params, at::Tensor grads, int64_t world, int64_t rank, py::list buckets,
-         int64_t max_slices, int64_t repl_bucket)
-      : params_(params), grads_(grads) {
+  PyPeerBase(at::Tensor params, at::Tensor grads) : params_(params), grads_(grads) {
     check_f32_cuda(params, "params");
     check_f32_cuda(grads, "grads");
     TORCH_CHECK(params.numel() == grads.numel(), "params/grads size mismatch");
+  }
+  py::bytes handle() const {
+    c10::hip::HIPGuard guard(device());
+    return py::bytes(p_->handle());
+  }
+  void open(std::vector<std::string> handles) {
+    c10::hip::HIPGuard guard(device());
+    p_->open(handles);
+  }
+  void unmap_peers() {
+    c10::hip::HIPGuard guard(device());
+    py::gil_scoped_release nogil;
+    p_->unmap_peers();
+  }
+  void close() {
+    c10::hip::HIPGuard guard(device());
+    py::gil_scoped_release nogil;
+    p_->close();
+  }
+  int error() const { return p_->error(); }
+  P* raw() { return p_.get(); }
+  int device() const { return params_.device().index(); }
+
+ protected:
+  at::Tensor params_, grads_;
+  std::unique_ptr<P> p_;
+};
+
+// xGMI peer exchange of the native sync step (kernels/xgmi.hip)
+class PyPeer : public PyPeerBase<ddl::PeerExchange> {
+ public:
+  PyPeer(at::Tensor params, at::Tensor grads, int64_t world, int64_t rank, py::list buckets,
+         int64_t max_slices, int64_t repl_bucket)
+      : PyPeerBase(params, grads) {
     // each bucket: (lo, hi) — an equal-chunk bucket — or (runs, state_offs, owner) — an owner
     // bucket of a tensor-granular plan (kernels/api.h XgmiBucketSpec)
     std::vector<ddl::XgmiBucketSpec> bk;
@@ -455,15 +544,6 @@ class PyPeer {
                                              params.numel(), (int)world, (int)rank, bk,
                                              (int)max_slices, (int)repl_bucket);
   }
-  py::bytes handle() const {
-    c10::hip::HIPGuard guard(params_.device().index());
-    return py::bytes(p_->handle());
-  }
-  void open(std::vector<std::string> handles) {
-    c10::hip::HIPGuard guard(params_.device().index());
-    p_->open(handles);
-  }
-  int error() const { return p_->error(); }
   // One bucket's exchange kernel on the current stream, as the runner launches it but with no
   // READY gate ahead: the kernels alone, on any small plan (tests/test_exchange_kernels_gpu.py).
   // kind: update.h's rule kind; step: Adam's lr_t, or the learning rate.  m and v are this rank's
@@ -474,10 +554,8 @@ class PyPeer {
               double mu, double scale, double coef, bool final_wait, double decay,
               bool nesterov) {
     TORCH_CHECK(bucket >= 0 && bucket < p_->num_buckets(), "bucket out of range");
-    TORCH_CHECK(kind >= 0 && kind <= 2, "update: rule kind");
     ddl::XgmiUpdate u;
-    u.rule = ddl::UpdRule((int)kind, (float)b1, (float)b2, (float)eps, (float)mu, (float)scale,
-                          (float)decay, nesterov);
+    u.rule = rule_of(kind, b1, b2, eps, mu, scale, decay, nesterov);
     u.step = (float)step;
     u.coef = (float)coef;
     auto state = [&](const at::Tensor& t, const char* name) {
@@ -499,55 +577,24 @@ class PyPeer {
     for (int b = 0; b < p_->num_buckets(); ++b) v.push_back(p_->nslices(b));
     return v;
   }
-  void unmap_peers() {
-    c10::hip::HIPGuard guard(params_.device().index());
-    py::gil_scoped_release nogil;
-    p_->unmap_peers();
-  }
-  void close() {
-    c10::hip::HIPGuard guard(params_.device().index());
-    py::gil_scoped_release nogil;
-    p_->close();
-  }
   // -1: equal-chunk bucket; else the rank hosting the owner bucket's PS
   int owner(int64_t b) const {
     TORCH_CHECK(b >= 0 && b < p_->num_buckets(), "bucket out of range");
     return p_->owner((int)b);
   }
-  ddl::PeerExchange* raw() { return p_.get(); }
-
- private:
-  at::Tensor params_, grads_;
-  std::unique_ptr<ddl::PeerExchange> p_;
 };
 
 // asynchronous PS over xGMI peer memory (kernels/xgmi_async.hip); kernels on the current stream
-class PyAsyncPeer {
+class PyAsyncPeer : public PyPeerBase<ddl::AsyncPeer> {
  public:
   PyAsyncPeer(at::Tensor params, at::Tensor grads, int64_t world, int64_t rank, py::list ranges,
               std::vector<int64_t> hosts, int64_t max_slices)
-      : params_(params), grads_(grads) {
-    check_f32_cuda(params, "params");
-    check_f32_cuda(grads, "grads");
-    TORCH_CHECK(params.numel() == grads.numel(), "params/grads size mismatch");
-    std::vector<std::pair<int64_t, int64_t>> rg;
-    for (auto r : ranges) {
-      auto t = r.cast<py::tuple>();
-      rg.emplace_back(t[0].cast<int64_t>(), t[1].cast<int64_t>());
-    }
+      : PyPeerBase(params, grads) {
     std::vector<int> h(hosts.begin(), hosts.end());
     c10::hip::HIPGuard guard(params.device().index());
     p_ = std::make_unique<ddl::AsyncPeer>(params.data_ptr<float>(), grads.data_ptr<float>(),
-                                          params.numel(), (int)world, (int)rank, rg, h,
-                                          (int)max_slices);
-  }
-  py::bytes handle() const {
-    c10::hip::HIPGuard guard(params_.device().index());
-    return py::bytes(p_->handle());
-  }
-  void open(std::vector<std::string> handles) {
-    c10::hip::HIPGuard guard(params_.device().index());
-    p_->open(handles);
+                                          params.numel(), (int)world, (int)rank,
+                                          index_ranges(ranges), h, (int)max_slices);
   }
   void push_all(int64_t epoch, double coef) { p_->push_all((uint32_t)epoch, (float)coef, cur_stream()); }
   void attach_done(std::string name, bool create) { p_->attach_done(name, create); }
@@ -562,32 +609,16 @@ class PyAsyncPeer {
              double b2, double eps, double lr, double mu, double scale, double weight_decay,
              bool nesterov) {
     check_f32_cuda(ps_params, "ps_params");
+    const ddl::OptimSpec s =
+        spec_of("apply", opt, lr, b1, b2, eps, mu, scale, weight_decay, nesterov);
     ddl::XgmiUpdate u;
-    u.rule = ddl::UpdRule((int)opt, (float)b1, (float)b2, (float)eps, (float)mu, (float)scale,
-                          ddl::upd_decay(lr, weight_decay), nesterov);
-    u.step = (float)(opt == ddl::kUpdMomentum ? lr : lr_t);
+    u.rule = s.rule;
+    u.step = s.step_for((float)lr_t);
     if (m) { check_f32_cuda(*m, "m"); u.m = m->data_ptr<float>(); }
     if (v) { check_f32_cuda(*v, "v"); u.v = v->data_ptr<float>(); }
     p_->apply((int)ps, (int)worker, (uint32_t)epoch, u, ps_params.data_ptr<float>(), cur_stream());
   }
-  void unmap_peers() {
-    c10::hip::HIPGuard guard(params_.device().index());
-    py::gil_scoped_release nogil;
-    p_->unmap_peers();
-  }
-  void close() {
-    c10::hip::HIPGuard guard(params_.device().index());
-    py::gil_scoped_release nogil;
-    p_->close();
-  }
-  int error() const { return p_->error(); }
-  ddl::AsyncPeer* raw() { return p_.get(); }
-  int device() const { return params_.device().index(); }
   const at::Tensor& grads() const { return grads_; }
-
- private:
-  at::Tensor params_, grads_;
-  std::unique_ptr<ddl::AsyncPeer> p_;
 };
 
 // native PS service thread of the async xGMI exchange
@@ -597,33 +628,11 @@ class PyAsyncService {
   PyAsyncService(PyAsyncPeer& peer, int64_t world, py::list ps, int64_t opt,
                  double lr, double b1, double b2, double eps, double mu, double scale,
                  int64_t epoch0, bool provenance, double weight_decay, bool nesterov) {
-    std::vector<ddl::AsyncPsState> st;
-    for (auto item : ps) {
-      auto t = item.cast<py::tuple>();
-      ddl::AsyncPsState s;
-      s.ps = t[0].cast<int>();
-      at::Tensor w = t[1].cast<at::Tensor>(), m = t[2].cast<at::Tensor>();
-      check_f32_cuda(w, "ps params");
-      check_f32_cuda(m, "m");
-      keep_.push_back(w);
-      keep_.push_back(m);
-      s.params = w.data_ptr<float>();
-      s.m = m.data_ptr<float>();
-      s.v = nullptr;
-      if (!t[3].is_none()) {
-        at::Tensor v = t[3].cast<at::Tensor>();
-        check_f32_cuda(v, "v");
-        keep_.push_back(v);
-        s.v = v.data_ptr<float>();
-      }
-      s.t = t[4].cast<int64_t>();
-      st.push_back(s);
-    }
-    svc_ = std::make_unique<ddl::AsyncService>(peer.raw(), (int)world, peer.device(), st,
-                                               (int)opt, (float)lr, (float)b1, (float)b2,
-                                               (float)eps, (float)mu, (float)scale,
-                                               (uint32_t)epoch0, provenance,
-                                               ddl::upd_decay(lr, weight_decay), nesterov);
+    svc_ = std::make_unique<ddl::AsyncService>(
+        peer.raw(), (int)world, peer.device(), ps_states(ps, keep_),
+        spec_of("async service", opt, lr, b1, b2, eps, mu, scale, weight_decay, nesterov,
+                /*f32=*/true),
+        (uint32_t)epoch0, provenance);
   }
   void start(int64_t expected) { svc_->start(expected); }
   void join() {
@@ -656,40 +665,15 @@ class PyRcclAsync {
       : params_(params), grads_(grads) {
     check_f32_cuda(params, "params");
     check_f32_cuda(grads, "grads");
-    std::vector<std::pair<int64_t, int64_t>> rg;
-    for (auto r : ranges) {
-      auto t = r.cast<py::tuple>();
-      rg.emplace_back(t[0].cast<int64_t>(), t[1].cast<int64_t>());
-    }
-    std::vector<ddl::AsyncPsState> st;
-    for (auto item : ps) {
-      auto t = item.cast<py::tuple>();
-      ddl::AsyncPsState s;
-      s.ps = t[0].cast<int>();
-      at::Tensor w = t[1].cast<at::Tensor>(), m = t[2].cast<at::Tensor>();
-      check_f32_cuda(w, "ps params");
-      check_f32_cuda(m, "m");
-      keep_.push_back(w);
-      keep_.push_back(m);
-      s.params = w.data_ptr<float>();
-      s.m = m.data_ptr<float>();
-      s.v = nullptr;
-      if (!t[3].is_none()) {
-        at::Tensor v = t[3].cast<at::Tensor>();
-        check_f32_cuda(v, "v");
-        keep_.push_back(v);
-        s.v = v.data_ptr<float>();
-      }
-      s.t = t[4].cast<int64_t>();
-      st.push_back(s);
-    }
     std::vector<int> h(hosts.begin(), hosts.end());
     c10::hip::HIPGuard guard(params.device().index());
-    r_ = std::make_unique<ddl::RcclAsync>(params.data_ptr<float>(), grads.data_ptr<float>(),
-                                          (int)world, (int)rank, params.device().index(), rg, h,
-                                          st, (int)opt, lr, b1, b2, (float)eps, (float)mu,
-                                          self_sessions, ddl::upd_decay(lr, weight_decay),
-                                          nesterov);
+    // (opt: Adam, else momentum; scale 1: the workers push unscaled gradients)
+    r_ = std::make_unique<ddl::RcclAsync>(
+        params.data_ptr<float>(), grads.data_ptr<float>(), (int)world, (int)rank,
+        params.device().index(), index_ranges(ranges), h, ps_states(ps, keep_),
+        spec_of("rccl async", opt == 0 ? ddl::kUpdAdam : ddl::kUpdMomentum, lr, b1, b2, eps, mu,
+                1.0, weight_decay, nesterov),
+        self_sessions);
   }
   void init_comm(py::bytes id) {
     std::string s = id;
@@ -736,28 +720,22 @@ class PyAsyncRunner {
     r_ = std::make_unique<ddl::AsyncRunner>(eng.raw(), peer.raw(), (int)world, (int)rank,
                                             peer.device(), seg, (uint32_t)epoch0);
   }
-  void step(at::Tensor x, at::Tensor labels, int64_t seed, double timeout_s) {
-    eng_.check_batch(x);
-    TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_cuda(), "labels must be int64 GPU");
-    TORCH_CHECK(labels.numel() == x.size(0), "labels/batch size mismatch");
-    const float* xp = x.data_ptr<float>();
-    const int64_t* lp = labels.data_ptr<int64_t>();
-    const int B = (int)x.size(0);
+  // step() or accumulate() of the native runner on one checked micro-batch
+  using Micro = void (ddl::AsyncRunner::*)(const float*, const int64_t*, int, uint32_t,
+                                           hipStream_t, double);
+  void micro(Micro f, const at::Tensor& x, const at::Tensor& labels, int64_t seed,
+             double timeout_s) {
+    const PyEngine::Batch b = eng_.batch(x, labels);
     hipStream_t st = cur_stream();
     py::gil_scoped_release nogil;  // the host wait for the previous round
-    r_->step(xp, lp, B, (uint32_t)(seed & 0xFFFFFFFF), st, timeout_s);
+    (r_.get()->*f)(b.x, b.labels, b.B, (uint32_t)(seed & 0xFFFFFFFF), st, timeout_s);
+  }
+  void step(at::Tensor x, at::Tensor labels, int64_t seed, double timeout_s) {
+    micro(&ddl::AsyncRunner::step, x, labels, seed, timeout_s);
   }
   // a non-final micro-batch of an accumulated round (set_accum)
   void accumulate(at::Tensor x, at::Tensor labels, int64_t seed, double timeout_s) {
-    eng_.check_batch(x);
-    TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_cuda(), "labels must be int64 GPU");
-    TORCH_CHECK(labels.numel() == x.size(0), "labels/batch size mismatch");
-    const float* xp = x.data_ptr<float>();
-    const int64_t* lp = labels.data_ptr<int64_t>();
-    const int B = (int)x.size(0);
-    hipStream_t st = cur_stream();
-    py::gil_scoped_release nogil;  // the host wait for the previous round
-    r_->accumulate(xp, lp, B, (uint32_t)(seed & 0xFFFFFFFF), st, timeout_s);
+    micro(&ddl::AsyncRunner::accumulate, x, labels, seed, timeout_s);
   }
   void finish(double timeout_s) {
     py::gil_scoped_release nogil;
@@ -780,28 +758,10 @@ class PyAsyncRunner {
   // ps: list of (ps id, private params, m, v, t), every PS (W = 1, Adam)
   void set_inline(py::list ps, double lr, double b1, double b2, double eps, double scale,
                   bool provenance, double weight_decay) {
-    std::vector<ddl::AsyncPsState> st;
-    for (auto item : ps) {
-      auto t = item.cast<py::tuple>();
-      ddl::AsyncPsState s;
-      s.ps = t[0].cast<int>();
-      at::Tensor w = t[1].cast<at::Tensor>(), m = t[2].cast<at::Tensor>();
-      TORCH_CHECK(!t[3].is_none(), "in-line applies are Adam: v required");
-      at::Tensor v = t[3].cast<at::Tensor>();
-      check_f32_cuda(w, "ps params");
-      check_f32_cuda(m, "m");
-      check_f32_cuda(v, "v");
-      keep_.push_back(w);
-      keep_.push_back(m);
-      keep_.push_back(v);
-      s.params = w.data_ptr<float>();
-      s.m = m.data_ptr<float>();
-      s.v = v.data_ptr<float>();
-      s.t = t[4].cast<int64_t>();
-      st.push_back(s);
-    }
-    r_->set_inline(st, (float)lr, (float)b1, (float)b2, (float)eps, (float)scale, provenance,
-                   ddl::upd_decay(lr, weight_decay));
+    r_->set_inline(ps_states(ps, keep_, /*need_v=*/true),
+                   spec_of("set_inline", ddl::kUpdAdam, lr, b1, b2, eps, 0.0, scale, weight_decay,
+                           false, /*f32=*/true),
+                   provenance);
   }
   bool inline_on() const { return r_->inline_on(); }
   int64_t inline_t(int64_t ps) const { return r_->inline_t((int)ps); }
@@ -906,11 +866,8 @@ class PyRunner {
   }
   void set_optimizer(int64_t kind, double lr, double b1, double b2, double eps, double mu,
                      double weight_decay, bool nesterov) {
-    TORCH_CHECK(weight_decay >= 0.0, "set_optimizer: negative weight decay");
-    TORCH_CHECK(!nesterov || kind == ddl::kUpdMomentum,
-                "set_optimizer: Nesterov needs the momentum rule");
-    r_->set_optimizer((int)kind, (float)lr, (float)b1, (float)b2, (float)eps, (float)mu,
-                      ddl::upd_decay(lr, weight_decay), nesterov);
+    r_->set_optimizer(
+        spec_of("set_optimizer", kind, lr, b1, b2, eps, mu, 1.0, weight_decay, nesterov));
   }
   void set_scale(double grad_scale, double coef) { r_->set_scale((float)grad_scale, (float)coef); }
   // clip the step's gradient by its global norm; out: {norm, coef} after each step (max_norm 0: off)
@@ -926,11 +883,8 @@ class PyRunner {
   }
   // a non-final micro-batch of an accumulated step (set_accum)
   void accumulate(at::Tensor x, at::Tensor labels, int64_t seed) {
-    eng_.check_batch(x);
-    TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_cuda(), "labels must be int64 GPU");
-    TORCH_CHECK(labels.numel() == x.size(0), "labels/batch size mismatch");
-    r_->accumulate(x.data_ptr<float>(), labels.data_ptr<int64_t>(), (int)x.size(0),
-                   (uint32_t)(seed & 0xFFFFFFFF), cur_stream());
+    const PyEngine::Batch b = eng_.batch(x, labels);
+    r_->accumulate(b.x, b.labels, b.B, (uint32_t)(seed & 0xFFFFFFFF), cur_stream());
   }
   void set_local_on_main(bool on) { r_->set_local_on_main(on); }
   void set_last_on_main(bool on) { r_->set_last_on_main(on); }
@@ -940,13 +894,10 @@ class PyRunner {
   void set_tail_cfg(int64_t first, int64_t f4) { r_->set_tail_cfg((int)first, (int)f4); }
   int64_t update_launches() const { return r_->update_launches(); }
   void step(at::Tensor x, at::Tensor labels, int64_t seed, std::vector<double> lr_t) {
-    eng_.check_batch(x);
-    TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_cuda(), "labels must be int64 GPU");
-    TORCH_CHECK(labels.numel() == x.size(0), "labels/batch size mismatch");
+    const PyEngine::Batch b = eng_.batch(x, labels);
     lr_.assign(lr_t.begin(), lr_t.end());
     if (lr_.empty()) lr_.push_back(0.f);
-    r_->step(x.data_ptr<float>(), labels.data_ptr<int64_t>(), (int)x.size(0),
-             (uint32_t)(seed & 0xFFFFFFFF), lr_.data(), cur_stream());
+    r_->step(b.x, b.labels, b.B, (uint32_t)(seed & 0xFFFFFFFF), lr_.data(), cur_stream());
   }
   std::string async_error() { return r_->async_error(); }
   void abort() { r_->abort(); }

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "clip_ranges.h"
+#include "ps_bank.h"
 #include "runtime/session.h"
 #include "schedule.h"
 #include "scratch.h"
@@ -268,13 +269,12 @@ void run_whole_backward(Engine& eng, const MicroBatch& mb);
 
 struct LocalUpdates {     // one worker, every update local (W = 1)
   const UpdatePlan* plan;
-  UpdRule rule;
-  float lr;               // the momentum rule's step size
+  const OptimSpec* opt;   // the rule, and the momentum rule's step size
   const float* lr_t;      // the Adam rule's, by PS
   float* w;
   const float* g;
   int max_grid = 2048;    // of a stand-alone launch
-  float step(const PlanPiece& p) const { return rule.kind == kUpdMomentum ? lr : lr_t[p.ps]; }
+  float step(const PlanPiece& p) const { return opt->step_for(lr_t[p.ps]); }
 };
 // launch_update of each piece; returns the launches issued
 int launch_piece_updates(const LocalUpdates& u, const std::vector<PlanPiece>& pieces,
@@ -493,7 +493,6 @@ class PeerExchange {
 };
 
 // ---- asynchronous PS over xGMI peer memory (xgmi_async.hip) ----------------------------------
-constexpr int kAsyncMaxPs = 64;
 constexpr int kAsyncMaxSlices = 512;
 // a rank's uncached device flags: its DONE words as a worker (dense over all PS' slices)
 constexpr int kAsyncDense = kAsyncMaxPs * kAsyncMaxSlices;
@@ -574,19 +573,10 @@ class AsyncPeer {
   bool done_owner_ = false;
 };
 
-struct AsyncPsState {            // one hosted PS as the service thread sees it
-  int ps;
-  float* params;                 // the PS's private parameter copy
-  float* m;
-  float* v;
-  int64_t t;                     // its step counter (advanced once per arrival)
-};
-
 class AsyncService {
  public:
   AsyncService(AsyncPeer* peer, int world, int device, const std::vector<AsyncPsState>& ps,
-               int opt, float lr, float b1, float b2, float eps, float mu, float scale,
-               uint32_t epoch0, bool provenance, float decay = 0.f, bool nesterov = false);
+               const OptimSpec& opt, uint32_t epoch0, bool provenance);
   ~AsyncService();
   void start(int64_t expected);  // serve `expected` pushes on a native thread
   void join();                   // rethrows the thread's error, if any
@@ -594,10 +584,10 @@ class AsyncService {
   // completed when pause() returns (the PS state is one consistent step); same caller thread
   void pause();
   void resume();
-  int64_t t(int ps) const;
+  int64_t t(int ps) const { return bank_.t(ps); }
   int64_t served() const;
   // (worker, ps, worker round, PS step) per apply, in service order
-  const std::vector<std::array<int64_t, 4>>& provenance() const { return prov_; }
+  const std::vector<std::array<int64_t, 4>>& provenance() const { return bank_.provenance(); }
   // the thread scans the board and launches each apply
   const char* mode() const { return "host"; }
 
@@ -606,12 +596,8 @@ class AsyncService {
   void serve(AsyncPsState& st, int worker);
   AsyncPeer* peer_;
   int world_, device_;
-  std::vector<AsyncPsState> ps_;
-  UpdRule rule_;
-  float lr_, b1_, b2_;           // widened to double for adam_step_size (update.h)
-  bool keep_prov_;
+  PsBank bank_;                  // the hosted PS, their optimizer and the provenance log
   std::vector<uint32_t> epoch_;
-  std::vector<std::array<int64_t, 4>> prov_;
   std::atomic<int64_t> served_{0};
   int64_t expected_ = 0;
   hipStream_t stream_ = nullptr;
@@ -658,13 +644,14 @@ class AsyncRunner {
   // DONE word or gate is needed; the PS's private parameter copy is not touched per step (it
   // equals the worker's buffer: inline_sync_ps() writes it back for checkpoints).  `ps` gives
   // every PS's m, v and t (its params pointer: the private copy).
-  void set_inline(const std::vector<AsyncPsState>& ps, float lr, float b1, float b2, float eps,
-                  float scale, bool provenance, float decay = 0.f);
+  void set_inline(const std::vector<AsyncPsState>& ps, const OptimSpec& opt, bool provenance);
   bool inline_on() const { return inline_; }
-  int64_t inline_t(int ps) const;
+  int64_t inline_t(int ps) const { return bank_.t(ps); }
   void inline_sync_ps(hipStream_t st);  // worker buffer -> every PS's private copy
   // (worker, ps, round, t) per in-line apply, when provenance was asked for
-  const std::vector<std::array<int64_t, 4>>& inline_provenance() const { return prov_; }
+  const std::vector<std::array<int64_t, 4>>& inline_provenance() const {
+    return bank_.provenance();
+  }
   // stand-alone optimizer launches of the most recent in-line step (SyncRunner::update_launches)
   int update_launches() const { return upd_launches_ + eng_->update_launches; }
 
@@ -674,14 +661,11 @@ class AsyncRunner {
   void wait_params(double timeout_s);
   void step_inline(const MicroBatch& mb);
   float* grads() const { return const_cast<float*>(peer_->grads()); }
-  bool inline_ = false, keep_prov_ = false;
-  std::vector<AsyncPsState> ips_;  // by PS id
+  bool inline_ = false;
+  PsBank bank_;                    // in-line: every PS, under Adam or AdamW (no other rule)
   UpdatePlan plan_;                // in-line: one piece per PS, its shard with its own m / v
   int upd_launches_ = 0;
-  UpdRule rule_;                   // Adam or AdamW (the in-line applies have no other rule)
-  float lr_ = 0.f, b1_ = 0.f, b2_ = 0.f;  // widened to double for adam_step_size (update.h)
   std::vector<float> lr_t_;        // this round's TF1 Adam step size per PS
-  std::vector<std::array<int64_t, 4>> prov_;
   hipStream_t last_st_ = nullptr;
   bool stepped_ = false;
   bool use_tail_ = true;
@@ -703,9 +687,8 @@ class RcclAsync {
  public:
   RcclAsync(float* params, float* grads, int world, int rank, int device,
             const std::vector<std::pair<int64_t, int64_t>>& ps_ranges,
-            const std::vector<int>& hosts, const std::vector<AsyncPsState>& hosted, int opt,
-            double lr, double b1, double b2, float eps, float mu, bool self_sessions,
-            float decay = 0.f, bool nesterov = false);
+            const std::vector<int>& hosts, const std::vector<AsyncPsState>& hosted,
+            const OptimSpec& opt, bool self_sessions);
   ~RcclAsync();
   void init_comm(const char id[128]);               // collective over all ranks
   void attach_shm(const std::string& job, bool create);  // session locks (rank 0 creates)
@@ -715,29 +698,25 @@ class RcclAsync {
   void join();
   void pause();
   void resume();
-  int64_t t(int ps) const;
+  int64_t t(int ps) const { return bank_.t(ps); }
   // a hosted PS's step counter before start() (resume: the checkpoint's t, restored after the
   // object was built — Adam's bias correction continues instead of restarting at t = 1)
   void set_t(int ps, int64_t t);
   int64_t served() const { return served_.load(); }
   // (worker, ps, that worker's round at this PS, PS step) per applied push
-  const std::vector<std::array<int64_t, 4>>& provenance() const { return prov_; }
+  const std::vector<std::array<int64_t, 4>>& provenance() const { return bank_.provenance(); }
 
  private:
   void loop();
   bool push_one(int p);
   void serve(int worker, int p);
   void apply(int p, int worker, const float* g);
-  AsyncPsState* state_of(int p);
   float* w_;
   float* g_;
   int world_, rank_, device_;
   std::vector<std::pair<int64_t, int64_t>> ranges_;
   std::vector<int> hosts_;
-  std::vector<AsyncPsState> ps_;
-  UpdRule rule_;                 // (scale 1: the workers push unscaled gradients)
-  float lr_;                     // momentum's step size
-  double lrd_, b1d_, b2d_;       // adam_step_size in true doubles, as ops/adam.py
+  PsBank bank_;                  // (rule scale 1: the workers push unscaled gradients)
   bool self_;
   void* comm_ = nullptr;
   hipStream_t cs_ = nullptr;
@@ -748,8 +727,6 @@ class RcclAsync {
   std::unique_ptr<ShmMailbox> mine_;
   std::unique_ptr<ShmMailbox> boxes_[kXgmiMaxPeers];
   std::vector<int64_t> count_;
-  bool keep_prov_ = false;
-  std::vector<std::array<int64_t, 4>> prov_;
   std::atomic<int64_t> served_{0};
   int64_t expected_ = 0;
   std::thread th_;
@@ -775,11 +752,10 @@ class SyncRunner {
   void init_comm(const char id[128], bool force = false);
   bool has_comm() const { return comm_ != nullptr; }
   void set_units(const std::vector<RunnerUnit>& units);
-  // decay: update.h upd_decay(lr, weight decay).  A modified rule rides wherever its base rule
-  // does: the tail-path conditions test the kind only.
-  void set_optimizer(int kind, float lr, float b1, float b2, float eps, float mu,
-                     float decay = 0.f, bool nesterov = false);
-  void set_scale(float grad_scale, float coef) { rule_.scale = grad_scale; coef_ = coef; }
+  // Adam or momentum; the rule's scale stays set_scale's.  A modified rule rides wherever its
+  // base rule does: the tail-path conditions test the kind only.
+  void set_optimizer(const OptimSpec& opt);
+  void set_scale(float grad_scale, float coef) { opt_.rule.scale = grad_scale; coef_ = coef; }
   // clip this worker's gradient by its global norm (clip.hip) after the fourth backward segment
   // and before anything consumes it.  The caller maps every unit to the last segment; the tail
   // and final-in-reduce placements are not taken, as with coef_ != 1.  max_norm 0: off
@@ -861,16 +837,14 @@ class SyncRunner {
   double gate_timeout_s_ = 20.0;  // DDL_XGMI_TIMEOUT_S
   uint32_t ready_epoch_ = 0;      // one per step
   std::vector<RunnerUnit> units_;
-  UpdRule rule_{kUpdAdam, 0.9f, 0.999f, 1e-8f, 0.9f, 1.f};  // (scale: set_scale's grad_scale)
-  float lr_ = 1e-4f;       // momentum's step size (Adam's lr_t comes with every step())
+  // (scale: set_scale's grad_scale; Adam's lr_t comes with every step())
+  OptimSpec opt_ = OptimSpec::from_doubles(kUpdAdam, 1e-4f, 0.9, 0.999, 1e-8f, 0.9f, 1.f);
   float coef_ = 1.f;
   GradStage stage_;
   // a range's parameter / optimizer-state span (state at state_off of the owning PS's m / v)
   UpdSpan span_of(const RunnerRange& r, float* m, float* v) const {
     return UpdSpan{w_ + r.lo, m + r.state_off, v ? v + r.state_off : nullptr};
   }
-  // the step size under the current rule, given the owning PS's Adam lr_t
-  float step_of(float lr_t) const { return rule_.kind == kUpdMomentum ? lr_ : lr_t; }
   bool local_on_main_ = true;
   bool last_on_main_ = true;
   bool all_local_ = false;

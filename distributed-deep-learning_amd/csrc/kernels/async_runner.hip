@@ -100,15 +100,14 @@ void AsyncRunner::wait_params(double timeout_s) {
   }
 }
 
-void AsyncRunner::set_inline(const std::vector<AsyncPsState>& ps, float lr, float b1, float b2,
-                             float eps, float scale, bool provenance, float decay) {
+void AsyncRunner::set_inline(const std::vector<AsyncPsState>& ps, const OptimSpec& opt,
+                             bool provenance) {
   const int P = peer_->num_ps();
   if (world_ != 1) throw std::invalid_argument("async runner: in-line applies need one worker");
   if ((int)ps.size() != P) throw std::invalid_argument("async runner: in-line applies need every PS");
-  std::vector<AsyncPsState> by(P, AsyncPsState{-1, nullptr, nullptr, nullptr, 0});
+  if (opt.rule.kind != kUpdAdam) throw std::invalid_argument("async runner: in-line applies are Adam");
+  PsBank bank("async runner: in-line", ps, P, opt, provenance);  // (one state per PS, m and v)
   for (const auto& s : ps) {
-    if (s.ps < 0 || s.ps >= P || by[s.ps].ps >= 0 || !s.params || !s.m || !s.v)
-      throw std::invalid_argument("async runner: in-line PS state (one per PS, Adam m and v)");
     int64_t lo = 0, n = 0;
     int host = -1;
     peer_->shard(s.ps, lo, n, host);
@@ -117,9 +116,8 @@ void AsyncRunner::set_inline(const std::vector<AsyncPsState>& ps, float lr, floa
         !aligned16(float_at(peer_->grads(), lo)) || !aligned16(float_at(s.m, 0)) ||
         !aligned16(float_at(s.v, 0)))
       throw std::invalid_argument("async runner: in-line PS buffers must be 16-B aligned");
-    by[s.ps] = s;
   }
-  ips_ = by;
+  bank_ = bank;
   // one piece per PS: its shard with its own m / v, after the segment that completes it
   plan_ = UpdatePlan();
   for (int sg = 0; sg < kSegments; ++sg)
@@ -127,33 +125,21 @@ void AsyncRunner::set_inline(const std::vector<AsyncPsState>& ps, float lr, floa
       int64_t lo = 0, n = 0;
       int host = -1;
       peer_->shard(p, lo, n, host);
-      plan_.add(sg, PlanPiece{lo, lo + n, 0, p, by[p].m, by[p].v});
+      plan_.add(sg, PlanPiece{lo, lo + n, 0, p, bank_.at(p).m, bank_.at(p).v});
     }
   plan_.finish(reinterpret_cast<uintptr_t>(peer_->params()),
                reinterpret_cast<uintptr_t>(peer_->grads()));
-  rule_ = UpdRule(kUpdAdam, b1, b2, eps, 0.f, scale, decay);
-  lr_ = lr;
-  b1_ = b1;
-  b2_ = b2;
-  keep_prov_ = provenance;
-  prov_.clear();
   lr_t_.assign(P, 0.f);
   inline_ = true;
 }
 
-int64_t AsyncRunner::inline_t(int ps) const {
-  if (!inline_ || ps < 0 || ps >= (int)ips_.size())
-    throw std::invalid_argument("async runner: no in-line PS " + std::to_string(ps));
-  return ips_[ps].t;
-}
-
 void AsyncRunner::inline_sync_ps(hipStream_t st) {
   if (!inline_) return;
-  for (size_t p = 0; p < ips_.size(); ++p) {
+  for (int p = 0; p < peer_->num_ps(); ++p) {
     int64_t lo = 0, n = 0;
     int host = -1;
-    peer_->shard((int)p, lo, n, host);
-    const hipError_t e = hipMemcpyAsync(ips_[p].params, peer_->params() + lo,
+    peer_->shard(p, lo, n, host);
+    const hipError_t e = hipMemcpyAsync(bank_.at(p).params, peer_->params() + lo,
                                         (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st);
     if (e != hipSuccess)
       throw std::runtime_error(std::string("async runner: PS copy: ") + hipGetErrorString(e));
@@ -164,12 +150,12 @@ void AsyncRunner::step_inline(const MicroBatch& mb) {
   ++epoch_;
   upd_launches_ = eng_->update_launches = 0;
   // one Adam step of each PS's own counter per push (TF1: lr_t = lr sqrt(1 - b2^t) / (1 - b1^t))
-  for (size_t p = 0; p < ips_.size(); ++p) {
-    const int64_t t = ++ips_[p].t;
-    lr_t_[p] = adam_step_size(lr_, b1_, b2_, t);
-    if (keep_prov_) prov_.push_back({(int64_t)rank_, (int64_t)p, (int64_t)epoch_, t});
+  for (int p = 0; p < (int)lr_t_.size(); ++p) {
+    const PsBank::Step s = bank_.advance(bank_.at(p));
+    lr_t_[p] = s.step;
+    bank_.record(rank_, p, epoch_, s.t);
   }
-  const LocalUpdates u{&plan_, rule_, lr_, lr_t_.data(), peer_->params(), peer_->grads()};
+  const LocalUpdates u{&plan_, &bank_.spec(), lr_t_.data(), peer_->params(), peer_->grads()};
   run_forward(*eng_, mb);
   if (stage_.whole()) {
     // the norm (and the mean over the micro-batches) needs the whole backward: no tails; finish

@@ -57,26 +57,21 @@ static ncclComm_t comm_of(void* c) { return reinterpret_cast<ncclComm_t>(c); }
 RcclAsync::RcclAsync(float* params, float* grads, int world, int rank, int device,
                      const std::vector<std::pair<int64_t, int64_t>>& ps_ranges,
                      const std::vector<int>& hosts, const std::vector<AsyncPsState>& hosted,
-                     int opt, double lr, double b1, double b2, float eps, float mu,
-                     bool self_sessions, float decay, bool nesterov)
+                     const OptimSpec& opt, bool self_sessions)
     : w_(params), g_(grads), world_(world), rank_(rank), device_(device), ranges_(ps_ranges),
-      hosts_(hosts), ps_(hosted),
-      rule_(opt == 0 ? kUpdAdam : kUpdMomentum, (float)b1, (float)b2, eps, mu, 1.f, decay,
-            nesterov),
-      lr_((float)lr), lrd_(lr), b1d_(b1), b2d_(b2), self_(self_sessions) {
+      hosts_(hosts), bank_("rccl async", hosted, (int)ps_ranges.size(), opt, false),
+      self_(self_sessions) {
   if (world < 1 || world > kXgmiMaxPeers) throw std::invalid_argument("rccl async: world");
   if (ranges_.size() != hosts_.size() || ranges_.empty())
     throw std::invalid_argument("rccl async: one host per PS range");
-  for (const auto& s : ps_) {
-    if (s.ps < 0 || s.ps >= (int)ranges_.size() || hosts_[s.ps] != rank_)
+  for (const auto& s : hosted)
+    if (hosts_[s.ps] != rank_)
       throw std::invalid_argument("rccl async: hosted PS state of a PS this rank does not host");
-    if (!s.params || !s.m || (opt == 0 && !s.v)) throw std::invalid_argument("rccl async: PS state");
-  }
   HIP_CHECK(hipSetDevice(device_));
   HIP_CHECK(hipStreamCreateWithFlags(&cs_, hipStreamNonBlocking));
   HIP_CHECK(hipEventCreateWithFlags(&ev_, hipEventDisableTiming));
   int64_t mx = 0;
-  for (const auto& s : ps_) mx = std::max(mx, ranges_[s.ps].second - ranges_[s.ps].first);
+  for (const auto& s : hosted) mx = std::max(mx, ranges_[s.ps].second - ranges_[s.ps].first);
   if (mx > 0) HIP_CHECK(hipMalloc(&gbuf_, mx * sizeof(float)));
   count_.assign((size_t)world * ranges_.size(), 0);
 }
@@ -116,28 +111,21 @@ void RcclAsync::open_boxes(bool own) {
       if (r != rank_) boxes_[r] = std::make_unique<ShmMailbox>(box_name_ + std::to_string(r), 2, false);
 }
 
-AsyncPsState* RcclAsync::state_of(int p) {
-  for (auto& s : ps_)
-    if (s.ps == p) return &s;
-  throw std::runtime_error("rccl async: PS " + std::to_string(p) + " not hosted here");
-}
-
 // One Adam (or momentum) step of hosted PS p from gradient g, on the comm stream.
 void RcclAsync::apply(int p, int worker, const float* g) {
-  AsyncPsState* st = state_of(p);
+  AsyncPsState& st = bank_.at(p);
   const int64_t n = ranges_[p].second - ranges_[p].first;
-  const int64_t t = __atomic_add_fetch(&st->t, 1, __ATOMIC_ACQ_REL);
-  // TF1 Adam's lr_t from true doubles, as ops/adam.py adam_coeffs (the same bits as the sync path)
-  const float step = rule_.kind == kUpdAdam ? adam_step_size(lrd_, b1d_, b2d_, t) : lr_;
-  launch_update(rule_, step, UpdSpan{st->params, st->m, st->v}, g, n, cs_);
+  // (TF1 Adam's lr_t from true doubles, OptimSpec::from_doubles: the same bits as the sync path)
+  const PsBank::Step s = bank_.advance(st);
+  launch_update(bank_.spec().rule, s.step, UpdSpan{st.params, st.m, st.v}, g, n, cs_);
   const int64_t k = ++count_[(size_t)worker * ranges_.size() + p];
-  if (keep_prov_) prov_.push_back({(int64_t)worker, (int64_t)p, k, t});
+  bank_.record(worker, p, k, s.t);
 }
 
 // PS side of a session with worker a (who holds both session locks)
 void RcclAsync::serve(int a, int p) {
   TraceRange r("ddl.async.rccl.serve");
-  AsyncPsState* st = state_of(p);
+  AsyncPsState* st = &bank_.at(p);
   const int64_t n = ranges_[p].second - ranges_[p].first;
   std::lock_guard<std::mutex> hold(pause_mu_);
   RCCL_CHECK(rccl().GroupStart());
@@ -157,7 +145,7 @@ bool RcclAsync::push_one(int p) {
   const int64_t lo = ranges_[p].first, n = ranges_[p].second - lo;
   if (h == rank_ && !self_) {  // own PS: no session
     std::lock_guard<std::mutex> hold(pause_mu_);
-    AsyncPsState* st = state_of(p);
+    AsyncPsState* st = &bank_.at(p);
     apply(p, rank_, g_ + lo);
     HIP_CHECK(hipMemcpyAsync(w_ + lo, st->params, n * sizeof(float), hipMemcpyDeviceToDevice, cs_));
     HIP_CHECK(hipStreamSynchronize(cs_));
@@ -165,7 +153,7 @@ bool RcclAsync::push_one(int p) {
   }
   if (h == rank_) {  // 1-rank rehearsal: the same exchange as send/recv to itself
     std::lock_guard<std::mutex> hold(pause_mu_);
-    AsyncPsState* st = state_of(p);
+    AsyncPsState* st = &bank_.at(p);
     RCCL_CHECK(rccl().GroupStart());
     RCCL_CHECK(rccl().Send(g_ + lo, (size_t)n, ncclFloat32, rank_, comm_of(comm_), cs_));
     RCCL_CHECK(rccl().Recv(gbuf_, (size_t)n, ncclFloat32, rank_, comm_of(comm_), cs_));
@@ -200,7 +188,7 @@ void RcclAsync::start(int64_t expected_served, bool provenance) {
   if (th_.joinable()) throw std::runtime_error("rccl async: already started");
   if (!comm_) throw std::runtime_error("rccl async: init_comm() first");
   expected_ = expected_served;
-  keep_prov_ = provenance;
+  bank_.keep_provenance(provenance);
   th_ = std::thread([this] { loop(); });
 }
 
@@ -277,14 +265,7 @@ void RcclAsync::resume() { pause_mu_.unlock(); }
 
 void RcclAsync::set_t(int p, int64_t t) {
   if (th_.joinable()) throw std::runtime_error("rccl async: set_t after start()");
-  if (t < 0) throw std::invalid_argument("rccl async: negative step counter");
-  __atomic_store_n(&state_of(p)->t, t, __ATOMIC_RELEASE);
-}
-
-int64_t RcclAsync::t(int p) const {
-  for (const auto& s : ps_)
-    if (s.ps == p) return __atomic_load_n(&s.t, __ATOMIC_ACQUIRE);
-  throw std::invalid_argument("rccl async: PS not hosted here");
+  bank_.set_t(p, t);
 }
 
 }  // namespace ddl

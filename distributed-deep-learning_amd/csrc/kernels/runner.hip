@@ -84,7 +84,7 @@ int launch_piece_updates(const LocalUpdates& u, const std::vector<PlanPiece>& pi
   int launches = 0;
   for (const auto& p : pieces) {
     const UpdSpan span{u.w + p.lo, p.m + p.state_off, p.v ? p.v + p.state_off : nullptr};
-    launch_update(u.rule, u.step(p), span, u.g + p.lo, p.n(), st, u.max_grid);
+    launch_update(u.opt->rule, u.step(p), span, u.g + p.lo, p.n(), st, u.max_grid);
     launches += p.n() > 0;
   }
   return launches;
@@ -95,7 +95,7 @@ int launch_piece_updates(const LocalUpdates& u, const std::vector<PlanPiece>& pi
 static UpdTail tail_of(const LocalUpdates& u, const std::vector<PlanPiece>& pieces, int first,
                        int f4_per_block) {
   UpdTail t;
-  t.rule = u.rule;
+  t.rule = u.opt->rule;
   t.first = first;
   t.f4_per_block = f4_per_block;
   for (const auto& p : pieces) {
@@ -103,7 +103,7 @@ static UpdTail tail_of(const LocalUpdates& u, const std::vector<PlanPiece>& piec
     q.w = u.w + p.lo;
     q.g = u.g + p.lo;
     q.m = p.m + p.state_off;
-    q.v = u.rule.kind == kUpdMomentum ? nullptr : p.v + p.state_off;
+    q.v = u.opt->rule.kind == kUpdMomentum ? nullptr : p.v + p.state_off;
     q.n = p.n();
     q.step = u.step(p);
     t.add_piece(q);
@@ -262,7 +262,7 @@ void SyncRunner::set_units(const std::vector<RunnerUnit>& units) {
         throw std::invalid_argument("the replicated xGMI bucket must be the last segment's");
       // (an owner bucket's optimizer state exists only on its owner rank)
       const bool owns = peer_->owner(u.bucket) < 0 || peer_->owner(u.bucket) == rank_;
-      if (owns && rule_.kind == kUpdAdam && !u.v) throw std::invalid_argument("xGMI unit without Adam state");
+      if (owns && opt_.rule.kind == kUpdAdam && !u.v) throw std::invalid_argument("xGMI unit without Adam state");
       if (peer_->owner(u.bucket) >= 0 && peer_->owner(u.bucket) != u.host)
         throw std::invalid_argument("xGMI owner bucket hosted on another rank than its unit");
     }
@@ -296,12 +296,12 @@ void SyncRunner::set_units(const std::vector<RunnerUnit>& units) {
   plan_.finish(reinterpret_cast<uintptr_t>(w_), reinterpret_cast<uintptr_t>(g_));
 }
 
-void SyncRunner::set_optimizer(int kind, float lr, float b1, float b2, float eps, float mu,
-                               float decay, bool nesterov) {
-  if (kind != kUpdAdam && kind != kUpdMomentum)
+void SyncRunner::set_optimizer(const OptimSpec& opt) {
+  if (opt.rule.kind != kUpdAdam && opt.rule.kind != kUpdMomentum)
     throw std::invalid_argument("native runner: adam or momentum");
-  rule_ = UpdRule(kind, b1, b2, eps, mu, rule_.scale, decay, nesterov);
-  lr_ = lr;
+  const float scale = opt_.rule.scale;
+  opt_ = opt;
+  opt_.rule.scale = scale;
 }
 
 // An update on the comm stream overlaps the backward's dual launches: fewer workgroups leave
@@ -314,7 +314,7 @@ void SyncRunner::set_optimizer(int kind, float lr, float b1, float b2, float eps
 #endif
 void SyncRunner::update(const UpdSpan& s, const float* g, int64_t n, float lr_t, hipStream_t st) {
   const int max_grid = st == cs_ ? DDL_COMM_ADAM_GRID : 2048;
-  launch_update(rule_, step_of(lr_t), s, g, n, st, max_grid);
+  launch_update(opt_.rule, opt_.step_for(lr_t), s, g, n, st, max_grid);
   upd_launches_ += n > 0;
 }
 
@@ -417,9 +417,9 @@ void SyncRunner::step(const float* x, const int64_t* labels, int B, uint32_t see
   // the remaining backward segments.
   run_forward(*eng_, mb);
   if (all_local_ && local_on_main_) {
-    const LocalUpdates u{&plan_, rule_, lr_, lr_t, w_, g_, st == cs_ ? DDL_COMM_ADAM_GRID : 2048};
+    const LocalUpdates u{&plan_, &opt_, lr_t, w_, g_, st == cs_ ? DDL_COMM_ADAM_GRID : 2048};
     // (Adam needs every piece's v; momentum / SGD have none and form none)
-    if (use_tail_ && plan_.tail_ok && (rule_.kind == kUpdMomentum || plan_.tail_v_ok) &&
+    if (use_tail_ && plan_.tail_ok && (opt_.rule.kind == kUpdMomentum || plan_.tail_v_ok) &&
         coef_ == 1.f && !whole) {
       const RidePolicy all_ride{{true, true, true, true}, tail_first_, tail_f4_, final_in_reduce_};
       upd_launches_ += run_riding_backward(*eng_, mb, u, all_ride);
@@ -558,8 +558,8 @@ void SyncRunner::issue_xgmi(const RunnerUnit& u, const float* lr_t, bool final_w
                             hipStream_t st, bool gated) {
   XgmiUpdate up;
   const auto& r = u.ranges[0];
-  up.rule = rule_;
-  up.step = step_of(lr_t[u.ps]);
+  up.rule = opt_.rule;
+  up.step = opt_.step_for(lr_t[u.ps]);
   // an owner bucket addresses its runs' state offsets itself (PeerExchange bucket spec)
   const bool own = peer_->owner(u.bucket) >= 0;
   up.m = u.m ? u.m + (own ? 0 : r.state_off) : nullptr;

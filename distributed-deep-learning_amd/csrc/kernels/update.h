@@ -55,8 +55,8 @@ struct UpdSpan {
 };
 
 // TF1 Adam's lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t) at step t (1-based), in double, as
-// ops/adam.py adam_coeffs.  The callers pass operands of different widths (float members widened,
-// or true doubles), which can differ in lr_t's last bit: docs/DESIGN.md.
+// ops/adam.py adam_coeffs.  Called by OptimSpec::step_at alone (ps_bank.h), whose two constructors
+// fix the operands' width (float32 widened, or true doubles: they can differ in lr_t's last bit).
 inline float adam_step_size(double lr, double b1, double b2, int64_t t) {
   return (float)(lr * sqrt(1.0 - pow(b2, (double)t)) / (1.0 - pow(b1, (double)t)));
 }

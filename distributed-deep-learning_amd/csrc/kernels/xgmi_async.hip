@@ -573,18 +573,12 @@ void AsyncPeer::gate(uint32_t epoch, hipStream_t st) {
 // Scans the arrival board of this host's PS and enqueues one apply per completed push on one PS
 // stream; no Python, no GIL, no hand-off thread on the critical path of any worker's round.
 AsyncService::AsyncService(AsyncPeer* peer, int world, int device,
-                           const std::vector<AsyncPsState>& ps, int opt, float lr, float b1,
-                           float b2, float eps, float mu, float scale, uint32_t epoch0,
-                           bool provenance, float decay, bool nesterov)
-    : peer_(peer), world_(world), device_(device), ps_(ps),
-      rule_(opt, b1, b2, eps, mu, scale, decay, nesterov), lr_(lr), b1_(b1), b2_(b2),
-      keep_prov_(provenance) {
+                           const std::vector<AsyncPsState>& ps, const OptimSpec& opt,
+                           uint32_t epoch0, bool provenance)
+    : peer_(peer), world_(world), device_(device),
+      bank_("async service", ps, peer->num_ps(), opt, provenance) {
   if (world < 1 || world > kXgmiMaxPeers) throw std::invalid_argument("async service: world");
-  for (const auto& s : ps)
-    if (s.ps < 0 || s.ps >= peer->num_ps() || !s.params || !s.m || (opt == 0 && !s.v))
-      throw std::invalid_argument("async service: PS state");
   epoch_.assign((size_t)world * kAsyncMaxPs, epoch0);
-  if ((int)ps.size() > kAsyncMaxPs) throw std::invalid_argument("async service: too many PS");
 }
 
 AsyncService::~AsyncService() {
@@ -619,21 +613,22 @@ void AsyncService::serve(AsyncPsState& st, int w) {
   std::lock_guard<std::mutex> hold(pause_mu_);  // pause(): no apply while a snapshot is taken
   const uint32_t e = ++epoch_[(size_t)w * kAsyncMaxPs + p];
   // one apply_gradients of this PS per arrival
-  const int64_t t = __atomic_add_fetch(&st.t, 1, __ATOMIC_ACQ_REL);
+  const PsBank::Step s = bank_.advance(st);
   XgmiUpdate u;
-  u.rule = rule_;
-  u.step = rule_.kind == kUpdMomentum ? lr_ : adam_step_size(lr_, b1_, b2_, t);
+  u.rule = bank_.spec().rule;
+  u.step = s.step;
   u.m = st.m;
   u.v = st.v;
   peer_->apply(p, w, e, u, st.params, stream_);
-  if (keep_prov_) prov_.push_back({(int64_t)w, (int64_t)p, (int64_t)e, t});
+  bank_.record(w, p, e, s.t);
   served_.fetch_add(1);
 }
 
 void AsyncService::run() {
   try {
     X_CHECK(hipSetDevice(device_));
-    const int np = (int)ps_.size();
+    std::vector<AsyncPsState>& ps = bank_.states();
+    const int np = (int)ps.size();
     const int pairs = np * world_;
     // per (hosted PS, worker): the first slice of the next round not yet seen posted
     std::vector<int> seen((size_t)pairs, 0);
@@ -645,13 +640,13 @@ void AsyncService::run() {
       int hit = -1;
       for (int i = 0; i < pairs && hit < 0; ++i) {
         const int q = (start + i) % pairs;
-        AsyncPsState& st = ps_[q / world_];
+        AsyncPsState& st = ps[q / world_];
         const int w = q % world_;
         const uint32_t next = epoch_[(size_t)w * kAsyncMaxPs + st.ps] + 1;
         if (peer_->posted(st.ps, w, next, seen[q])) hit = q;
       }
       if (hit >= 0) {
-        serve(ps_[hit / world_], hit % world_);
+        serve(ps[hit / world_], hit % world_);
         seen[hit] = 0;
         start = hit + 1;
         ++k;
@@ -700,13 +695,6 @@ void AsyncService::pause() {
 
 void AsyncService::resume() {
   pause_mu_.unlock();
-}
-
-int64_t AsyncService::t(int ps) const {
-  for (size_t i = 0; i < ps_.size(); ++i)  // lock-free: also read while paused
-    if (ps_[i].ps == ps)
-      return __atomic_load_n(&ps_[i].t, __ATOMIC_ACQUIRE);
-  throw std::invalid_argument("async service: PS not hosted here");
 }
 
 int64_t AsyncService::served() const {
