@@ -23,6 +23,7 @@
 #include "schedule.h"
 #include "scratch.h"
 #include "tail.h"
+#include "xgmi_plan.h"
 
 namespace ddl {
 
@@ -331,56 +332,11 @@ struct RunnerUnit {
 };
 
 // ---- parameter-server exchange over xGMI peer memory (xgmi.hip) ------------------------------
-constexpr int kXgmiMaxPeers = 16;
-// flat plans: one bucket per backward segment (<= 8); tensor-granular plans: one OWNER bucket per
-// (PS, segment) exchange unit (<= 8 PS x 4 segments)
-constexpr int kXgmiMaxBuckets = 32;
-constexpr int kXgmiMaxRuns = 8;   // plan-buffer ranges of one owner bucket
-#ifndef DDL_XGMI_MAX_SLICES
-#define DDL_XGMI_MAX_SLICES 512
-#endif
-constexpr int kXgmiMaxSlices = DDL_XGMI_MAX_SLICES;
+// The limits, XgmiLaunch, XgmiBucketSpec and the slice and inbox plan: xgmi_plan.h.
 struct XgmiTable {               // every rank's IPC-mapped buffers, indexed by rank
   float* params[kXgmiMaxPeers];
   float* inbox[kXgmiMaxPeers];
   uint32_t* flags[kXgmiMaxPeers];
-};
-struct XgmiLaunch {              // one bucket's kernel arguments
-  int world, rank, bucket, nbuckets, final_wait;
-  uint32_t epoch;
-  int64_t lo, c, inbox_off, slice;
-  int nslices[kXgmiMaxBuckets];
-  const float* grads;
-  float* m;
-  float* v;
-  UpdRule rule;                  // the owner-side update (update.h) and its step size
-  float step, coef;
-  int* err;
-  long long timeout_ticks;
-  int check;                     // DDL_XGMI_CHECK: per-(bucket, source, slice) inbox checksums
-  int repl_bucket;               // the replicated bucket (-1: none)
-  int owners[kXgmiMaxBuckets];   // -1: chunk r of the bucket on rank r; >= 0: single owner rank
-  // the READY gate ahead of this kernel on the comm stream timed out (host word, or null): the
-  // segment's gradients may be incomplete, so the kernel publishes nothing (no pushes, no
-  // ARRIVE / DONE words); the peers then time out too and every host raises
-  const int* gate_err;
-  // owner buckets: the launched bucket's runs (plan-buffer range, element offset in the owner
-  // PS's optimizer state, offset in the bucket's concatenation, slice size, first slice)
-  int owner, nruns;
-  int64_t run_lo[kXgmiMaxRuns], run_n[kXgmiMaxRuns], run_soff[kXgmiMaxRuns];
-  int64_t run_voff[kXgmiMaxRuns], run_slice[kXgmiMaxRuns];
-  int run_sl0[kXgmiMaxRuns + 1];
-  int64_t rslot;                 // the replicated bucket's inbox slot stride (floats)
-};
-// One bucket of a PeerExchange.  owner < 0: a single plan-buffer range split into W equal chunks,
-// chunk r owned by rank r (the flat plan: reduce-scatter form).  owner >= 0: one PS's exchange
-// unit of a tensor-granular plan (reference none / contiguous / greedy, lpt; or a flat plan with
-// fewer PS than ranks) — every rank pushes the whole unit to its owner, which sums, updates with
-// that PS's optimizer state (run r at state_offs[r]) and pushes the parameters to every rank.
-struct XgmiBucketSpec {
-  std::vector<std::pair<int64_t, int64_t>> runs;
-  std::vector<int64_t> state_offs;
-  int owner = -1;
 };
 struct XgmiUpdate {              // owner-side update of one bucket chunk
   UpdRule rule;                  // update.h (kUpdCopy: the self-test, w := summed g)
@@ -454,14 +410,14 @@ class PeerExchange {
   void open(const std::vector<std::string>& handles) { map_.open(handles); }
   double timeout_s() const { return map_.timeout_s; }
   int num_buckets() const { return (int)bk_.size(); }
-  int nslices(int b) const { return bk_[b].nslice; }
+  int nslices(int b) const { return bk_[b].nslices[b]; }
   int64_t chunk(int b) const { return bk_[b].c; }
-  int owner(int b) const { return bk_[b].owner; }
+  int owner(int b) const { return bk_[b].owners[b]; }
   // elements of optimizer state a launch of bucket b may touch: [0, state_extent(b)) of m and v
   int64_t state_extent(int b) const {
-    const Bucket& B = bk_[b];
-    int64_t n = B.owner >= 0 ? 0 : B.c;
-    for (size_t r = 0; r < B.run_soff.size(); ++r)
+    const XgmiLaunch& B = bk_[b];
+    int64_t n = owner(b) >= 0 ? 0 : B.c;
+    for (int r = 0; r < B.nruns; ++r)
       if (B.run_soff[r] + B.run_n[r] > n) n = B.run_soff[r] + B.run_n[r];
     return n;
   }
@@ -470,14 +426,6 @@ class PeerExchange {
   bool check_mode() const { return check_; }
 
  private:
-  struct Bucket {
-    int64_t lo, c, inbox_off, slice;
-    int64_t slot = 0;  // the replicated bucket: floats per (parity, source) inbox slot
-    int nslice;
-    int owner = -1;
-    std::vector<int64_t> run_lo, run_n, run_soff, run_voff, run_slice;
-    std::vector<int> run_sl0;
-  };
   void init(const std::vector<XgmiBucketSpec>& buckets, int max_slices);
   void fill(int bucket, uint32_t epoch, const XgmiUpdate& u, bool final_wait, bool gated,
             XgmiLaunch& a) const;
@@ -487,21 +435,16 @@ class PeerExchange {
   const float* grads_;
   int64_t total_;
   int world_, rank_;
-  std::vector<Bucket> bk_;
+  // each bucket's launch record, every field set but the per-launch ones (fill)
+  std::vector<XgmiLaunch> bk_;
   PeerMap map_;
   const int* gate_err_ = nullptr;
 };
 
 // ---- asynchronous PS over xGMI peer memory (xgmi_async.hip) ----------------------------------
-constexpr int kAsyncMaxSlices = 512;
 // a rank's uncached device flags: its DONE words as a worker (dense over all PS' slices)
 constexpr int kAsyncDense = kAsyncMaxPs * kAsyncMaxSlices;
 constexpr size_t kAsyncFlagWords = (size_t)kAsyncDense;
-struct AsyncShard {              // one PS's contiguous range of the flat buffer
-  int64_t lo, n, slice, inbox_off;
-  int host, nslice;
-  int slice0;                    // its first slice in the dense numbering of all PS' slices
-};
 struct AsyncTable {
   float* params[kXgmiMaxPeers];  // every rank's worker parameter buffer (IPC-mapped)
   float* inbox[kXgmiMaxPeers];

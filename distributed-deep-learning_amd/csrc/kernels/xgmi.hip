@@ -46,27 +46,6 @@ namespace ddl {
 
 namespace {
 
-constexpr unsigned kSys = 1u | 16u;  // buffer-op cache policy: sc0 | sc1 = system coherent
-
-DDL_DEV void st4_sys(brsrc_t r, int byte_off, float4 v) {
-  __builtin_amdgcn_raw_buffer_store_b128(
-      __builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned int, v), r, byte_off, 0,
-      kSys);
-}
-DDL_DEV float4 ld4_sys(brsrc_t r, int byte_off) {
-  auto v = __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, kSys);
-  return *reinterpret_cast<float4*>(&v);
-}
-DDL_DEV void drain_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-// the flag protocol's device side lives in xgmi_dev.h
-DDL_DEV void flag_store(uint32_t* f, uint32_t v) { xg_flag_store(f, v); }
-DDL_DEV int arrive_idx(int b, int src, int j) { return xg_arrive_idx(b, src, j); }
-DDL_DEV int done_idx(int b, int src, int j) { return xg_done_idx(b, src, j); }
-DDL_DEV bool wait_ge(const uint32_t* f, uint32_t target, long long deadline, int* err, int code) {
-  return xg_wait_ge(f, target, deadline, err, code);
-}
-
 // The READY gate ahead of this kernel timed out (its gradients may be incomplete): publish
 // nothing, record error 6 (the peers' waits then time out as well and every host raises).
 DDL_DEV bool gate_failed(const XgmiLaunch& a) {
@@ -94,7 +73,7 @@ DDL_DEV float4 scale4(float4 x, float a) {
 // parity: a pusher writes an owner's inbox again only after that owner's DONE, i.e. after its
 // check.
 DDL_DEV int ck_idx(int b, int src, int j, int par = 0) {
-  return (2 + par) * kXgmiMaxBuckets * kXgmiMaxPeers * kXgmiMaxSlices + arrive_idx(b, src, j);
+  return (2 + par) * kXgmiMaxBuckets * kXgmiMaxPeers * kXgmiMaxSlices + xg_arrive_idx(b, src, j);
 }
 
 DDL_DEV uint32_t bits4(float4 v) {
@@ -111,27 +90,122 @@ DDL_DEV uint32_t block_sum(uint32_t v, uint32_t* red) {
   return t;
 }
 
-// owner-side check of one source's piece [n4 float4 at byte offset off of `in`]: false (error
-// code 3 recorded) when it differs from the checksum the source published
-DDL_DEV bool check_piece(brsrc_t in, int off, int n4, const uint32_t* ck, int* err,
-                         uint32_t* red) {
-  uint32_t c = 0;
-  for (int i = threadIdx.x; i < n4; i += 256) c += bits4(ld4_sys(in, off + i * 16));
-  const uint32_t got = block_sum(c, red);
-  const uint32_t want = __hip_atomic_load(ck, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  if (got == want) return true;
-  if (threadIdx.x == 0) __hip_atomic_store(err, 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  return false;
+// ---- the steps of a slice's round, written once; the three kernels below compose them ---------
+
+// Source q's piece of the slice in this rank's inbox: a descriptor and the byte offset of the
+// piece's first float4.  Each kernel hands the steps its inbox addressing as a functor q -> Piece.
+struct Piece {
+  brsrc_t in;
+  int off;
+};
+// What a workgroup knows of its round, read from the arguments once at the kernel's start (a
+// value reloaded from them further down, past a divergent branch, would count as divergent and
+// take the rank loops' addresses out of the scalar unit).
+struct Round {
+  int W, me, b, j;        // world size, this rank, the bucket, the slice
+  long long deadline;     // of every wait of this launch
+  uint32_t* myflags;
+  uint32_t* red;          // LDS: block_sum's 4 words
+  int* arrived;           // LDS: cleared when the wait or the check of the slice failed
+};
+
+// Every storing wave drains its write-through stores, the workgroup meets, and only then the
+// chosen lanes store `epoch` into word `word` of rank dst's flags (xgmi_dev.h: why the drain is
+// enough and no L2 write-back is needed).
+DDL_DEV void publish(const XgmiTable& T, bool lane, int dst, int word, uint32_t epoch) {
+  drain_vmem();
+  __syncthreads();
+  if (lane) xg_flag_store(T.flags[dst] + word, epoch);
 }
 
-// The final wait of a step (xgmi_dev.h xg_final_wait) over every thread of the launch.
-DDL_DEV void final_wait(const XgmiLaunch& a, const uint32_t* myflags, int W, long long deadline) {
-  xg_final_wait(a, a.epoch, myflags, W, deadline, blockIdx.x * 256 + threadIdx.x,
-                gridDim.x * 256);
+// The ARRIVE wait: every peer's piece of slice j has arrived (one parallel poll, lane q for peer
+// q).  *arrived (LDS) ends 0 if any wait failed (timeout, or another workgroup's recorded error).
+DDL_DEV void wait_arrivals(const XgmiLaunch& a, const Round& g) {
+  const int tid = threadIdx.x;
+  if (tid == 0) *g.arrived = 1;
+  __syncthreads();
+  if (tid < g.W && tid != g.me &&
+      !xg_wait_ge(g.myflags + xg_arrive_idx(g.b, tid, g.j), a.epoch, g.deadline, a.err, 1))
+    *g.arrived = 0;  // benign race: every writer stores 0
+  __syncthreads();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");  // keep the loads below the poll
 }
 
-// WT = world size when instantiated for it (loops over ranks fully unrolled: all of an
-// element's remote loads / stores are in flight together), 0 = any world size.
+// Check mode: every peer's piece (n4 float4) against the checksum it published; a mismatch
+// records error code 3 and clears *arrived.  par: the replicated bucket's step parity.
+template <class P>
+DDL_DEV void verify_pieces(const XgmiLaunch& a, const Round& g, int par, int n4, P piece) {
+  if (!a.check || !*g.arrived) return;
+  bool ok = true;
+  for (int q = 0; q < g.W; ++q) {
+    if (q == g.me) continue;
+    const Piece p = piece(q);
+    uint32_t c = 0;
+    for (int i = threadIdx.x; i < n4; i += 256) c += bits4(bload4_sys(p.in, p.off + i * 16));
+    const uint32_t got = block_sum(c, g.red);
+    const uint32_t want = __hip_atomic_load(g.myflags + ck_idx(g.b, q, g.j, par), __ATOMIC_RELAXED,
+                                            __HIP_MEMORY_SCOPE_SYSTEM);
+    ok &= got == want;
+  }
+  if (!ok && threadIdx.x == 0) {
+    __hip_atomic_store(a.err, 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    *g.arrived = 0;
+  }
+  __syncthreads();
+}
+
+// Reduce and update the slice's n4 float4: parameters and own gradient at element `po` of this
+// rank's buffers, optimizer state at element `so`, the peers' pieces through `piece`.  The W
+// contributions (the own one scaled by coef, as the pushed ones were) are summed from zero in
+// rank order: the same bits on every run, every rank and every rank count, and the RCCL reduce's.
+// If the wait or the check failed the slice is NOT updated: summing a stale inbox would advance
+// m / v and push wrong parameters into every replica.  The kernels still store DONE, so the peers
+// do not wait out their own timeouts; the host raises on the error word.
+// ALL: the new parameters go to every rank's copy, this one included, write-through, so a later
+// kernel of any rank (other XCD, other GPU) reads them from memory even while this kernel is
+// still running; workgroup j starts at a different rank.  Else to this rank's copy only (the
+// next forward is a later kernel of this stream).
+// NQ = world size when instantiated for it (loops over ranks fully unrolled: all of an element's
+// remote loads / stores are in flight together), else kXgmiMaxPeers.
+template <int NQ, bool ALL, class P>
+DDL_DEV void reduce_update(const XgmiTable& T, const XgmiLaunch& a, const Round& g, P piece,
+                           int64_t po, int64_t so, int n4) {
+  const int W = g.W, me = g.me, j = g.j;
+  const int n4u = *g.arrived ? n4 : 0;
+  const float4* own = reinterpret_cast<const float4*>(a.grads + po);
+  float4* m4 = a.m ? reinterpret_cast<float4*>(a.m + so) : nullptr;
+  float4* v4 = a.v ? reinterpret_cast<float4*>(a.v + so) : nullptr;
+  float4* w4 = reinterpret_cast<float4*>(T.params[me] + po);
+  for (int i = threadIdx.x; i < n4u; i += 256) {
+    float4 x[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      if (q >= W) continue;
+      if (q == me) {
+        x[q] = a.coef != 1.f ? scale4(own[i], a.coef) : own[i];
+      } else {
+        const Piece p = piece(q);
+        x[q] = bload4_sys(p.in, p.off + i * 16);
+      }
+    }
+    float4 w = w4[i];
+    float4 sum = f4zero();
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+      if (q < W) { sum.x += x[q].x; sum.y += x[q].y; sum.z += x[q].z; sum.w += x[q].w; }
+    upd4_any(a.rule, a.step, w, sum, m4, v4, i);
+    if (ALL) {
+#pragma unroll
+      for (int k = 0; k < NQ; ++k)
+        if (k < W)
+          bstore4_sys(make_rsrc(T.params[(me + k + j) % W] + po, (uint32_t)n4 * 16u), i * 16, w);
+    } else {
+      w4[i] = w;
+    }
+  }
+}
+
+// WT = world size when instantiated for it, 0 = any world size (reduce_update's NQ).
 template <int WT>
 __global__ void __launch_bounds__(256) xgmi_ps_kernel(XgmiTable T, XgmiLaunch a) {
   if (gate_failed(a)) return;
@@ -139,12 +213,14 @@ __global__ void __launch_bounds__(256) xgmi_ps_kernel(XgmiTable T, XgmiLaunch a)
   const int j = blockIdx.x, tid = threadIdx.x;
   const int W = WT ? WT : a.world, me = a.rank, b = a.bucket;
   const long long deadline = wall_clock64() + a.timeout_ticks;
-  const int64_t s0 = (int64_t)j * a.slice;
-  const int64_t s1 = s0 + a.slice < a.c ? s0 + a.slice : a.c;
-  const int n4 = s0 < s1 ? (int)((s1 - s0) >> 2) : 0;
+  const XgSlice s = xg_slice(j, a.slice, a.c);
+  const int64_t s0 = s.s0;
+  const int n4 = s.n4;
+  const int64_t po = a.lo + me * a.c + s0;  // my chunk's slice in the plan buffer
   uint32_t* myflags = T.flags[me];
   __shared__ uint32_t red[4];
   __shared__ int arrived;
+  const Round g{W, me, b, j, deadline, myflags, red, &arrived};
 
   // ---- phase 1: push my gradient pieces to their owners.  Per element index every owner's
   // load is issued before the first store; workgroup j starts at a different owner so the
@@ -168,7 +244,7 @@ __global__ void __launch_bounds__(256) xgmi_ps_kernel(XgmiTable T, XgmiLaunch a)
         const brsrc_t dst = make_rsrc(T.inbox[r] + a.inbox_off + (int64_t)me * a.c + s0,
                                       (uint32_t)n4 * 16u);
         const float4 v = a.coef != 1.f ? scale4(x[k], a.coef) : x[k];
-        st4_sys(dst, i * 16, v);
+        bstore4_sys(dst, i * 16, v);
         if (a.check) cs[k] += bits4(v);
       }
     }
@@ -185,68 +261,18 @@ __global__ void __launch_bounds__(256) xgmi_ps_kernel(XgmiTable T, XgmiLaunch a)
       }
     }
   }
-  drain_vm();
-  __syncthreads();
-  if (tid < W && tid != me) flag_store(T.flags[tid] + arrive_idx(b, me, j), a.epoch);
+  publish(T, tid < W && tid != me, tid, xg_arrive_idx(b, me, j), a.epoch);
 
-  // ---- phase 2: every peer's piece of my slice has arrived (one parallel poll).  If any wait
-  // failed (timeout, or another workgroup's recorded error) the slice is NOT updated: summing a
-  // stale inbox would advance m / v and push wrong parameters into every replica.  DONE is still
-  // stored, so the peers do not wait out their own timeouts; the host raises on the error word.
-  if (tid == 0) arrived = 1;
-  __syncthreads();
-  if (tid < W && tid != me &&
-      !wait_ge(myflags + arrive_idx(b, tid, j), a.epoch, deadline, a.err, 1))
-    arrived = 0;  // benign race: every writer stores 0
-  __syncthreads();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");  // keep the loads below the poll
-
+  // ---- phase 2: my chunk's slice, from every peer's slot [q] of my inbox, to every rank
   const brsrc_t inbox = make_rsrc(T.inbox[me] + a.inbox_off, (uint32_t)(W * a.c * 4));
-  if (a.check && arrived) {
-    bool ok = true;
-    for (int q = 0; q < W; ++q)
-      if (q != me)
-        ok &= check_piece(inbox, (int)(((int64_t)q * a.c + s0) * 4), n4,
-                          myflags + ck_idx(b, q, j), a.err, red);
-    if (!ok && tid == 0) arrived = 0;
-    __syncthreads();
-  }
-  const int n4u = arrived ? n4 : 0;
-
-  const float4* own = reinterpret_cast<const float4*>(a.grads + a.lo + me * a.c + s0);
-  float4* m4 = reinterpret_cast<float4*>(a.m + s0);
-  float4* v4 = a.v ? reinterpret_cast<float4*>(a.v + s0) : nullptr;
-  float4* w4 = reinterpret_cast<float4*>(T.params[me] + a.lo + me * a.c + s0);
-  for (int i = tid; i < n4u; i += 256) {
-    float4 x[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-      if (q < W)
-        x[q] = q == me ? (a.coef != 1.f ? scale4(own[i], a.coef) : own[i])
-                       : ld4_sys(inbox, (int)(((int64_t)q * a.c + s0) * 4) + i * 16);
-    float4 w = w4[i];
-    float4 g = f4zero();
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)  // rank order: the same sum on every run and every rank count
-      if (q < W) { g.x += x[q].x; g.y += x[q].y; g.z += x[q].z; g.w += x[q].w; }
-    upd4_any(a.rule, a.step, w, g, m4, v4, i);
-    // every rank's copy, this one included: write-through, so a later kernel of any rank
-    // (other XCD, other GPU) reads it from memory even while this kernel is still running
-#pragma unroll
-    for (int k = 0; k < NQ; ++k) {
-      if (k < W) {
-        const int q = (me + k + j) % W;
-        const brsrc_t dst = make_rsrc(T.params[q] + a.lo + me * a.c + s0, (uint32_t)n4 * 16u);
-        st4_sys(dst, i * 16, w);
-      }
-    }
-  }
-  drain_vm();
-  __syncthreads();
-  if (tid < W) flag_store(T.flags[tid] + done_idx(b, me, j), a.epoch);
+  auto piece = [&](int q) { return Piece{inbox, (int)(((int64_t)q * a.c + s0) * 4)}; };
+  wait_arrivals(a, g);
+  verify_pieces(a, g, 0, n4, piece);
+  reduce_update<NQ, true>(T, a, g, piece, po, s0, n4);
+  publish(T, tid < W, tid, xg_done_idx(b, me, j), a.epoch);
 
   // ---- final wait: every bucket's new parameters from every owner have landed here
-  if (a.final_wait) final_wait(a, myflags, W, deadline);
+  if (a.final_wait) xg_final_wait(a, myflags, W, deadline);
 }
 
 // The step's LAST bucket, replicated: nothing overlaps its exchange — it is
@@ -254,12 +280,13 @@ __global__ void __launch_bounds__(256) xgmi_ps_kernel(XgmiTable T, XgmiLaunch a)
 // push parameters -> DONE (two cross-GPU hops on the critical path), every rank pushes the
 // WHOLE bucket gradient to every peer (W-1 links at once, 208 KB each for conv1+conv2), sums the
 // W contributions in rank order and runs the update itself on replicated optimizer state, then
-// stores only its own parameters.  One hop.  The inbox has two parity slots per source: a peer
-// writes slot (e+1)&1 of step e+1 while this rank may still read slot e&1; it can write slot e&1
-// again only at step e+2, after its final wait of step e+1 saw this rank's DONE of every owner
-// bucket at e+1 — issued after this rank's step-e+1 forward, i.e. after this kernel of step e.
-// This needs the replicated bucket to be the one the last backward segment completes (conv1 +
-// conv2, launched on the compute stream): parallel/native_exchange.py last_segment_bucket.
+// stores only its own parameters.  One hop, and no DONE words.  The inbox has two parity slots
+// per source: a peer writes slot (e+1)&1 of step e+1 while this rank may still read slot e&1; it
+// can write slot e&1 again only at step e+2, after its final wait of step e+1 saw this rank's
+// DONE of every owner bucket at e+1 — issued after this rank's step-e+1 forward, i.e. after this
+// kernel of step e.  This needs the replicated bucket to be the one the last backward segment
+// completes (conv1 + conv2, launched on the compute stream): parallel/native_exchange.py
+// last_segment_bucket.
 template <int WT>
 __global__ void __launch_bounds__(256) xgmi_repl_kernel(XgmiTable T, XgmiLaunch a) {
   if (gate_failed(a)) return;
@@ -267,14 +294,14 @@ __global__ void __launch_bounds__(256) xgmi_repl_kernel(XgmiTable T, XgmiLaunch 
   const int j = blockIdx.x, tid = threadIdx.x;
   const int W = WT ? WT : a.world, me = a.rank, b = a.bucket;
   const long long deadline = wall_clock64() + a.timeout_ticks;
-  const int64_t n = a.c;  // replicated: the whole bucket
-  const int64_t s0 = (int64_t)j * a.slice;
-  const int64_t s1 = s0 + a.slice < n ? s0 + a.slice : n;
-  const int n4 = s0 < s1 ? (int)((s1 - s0) >> 2) : 0;
+  const XgSlice s = xg_slice(j, a.slice, a.c);  // replicated: a.c is the whole bucket
+  const int64_t s0 = s.s0;
+  const int n4 = s.n4;
   const int par = (int)(a.epoch & 1u);
   uint32_t* myflags = T.flags[me];
   __shared__ uint32_t red[4];
   __shared__ int arrived;
+  const Round g{W, me, b, j, deadline, myflags, red, &arrived};
   const float4* own = reinterpret_cast<const float4*>(a.grads + a.lo + s0);
   // slot (par, src) of rank r's replicated inbox, this slice
   auto slot = [&](int r, int src) {
@@ -290,7 +317,7 @@ __global__ void __launch_bounds__(256) xgmi_repl_kernel(XgmiTable T, XgmiLaunch 
     if (a.check) cs += bits4(x);
 #pragma unroll
     for (int k = 0; k < NQ - 1; ++k)
-      if (k < W - 1) st4_sys(slot((me + 1 + (k + j) % (W - 1)) % W, me), i * 16, x);
+      if (k < W - 1) bstore4_sys(slot((me + 1 + (k + j) % (W - 1)) % W, me), i * 16, x);
   }
   if (a.check) {
     const uint32_t t = block_sum(cs, red);
@@ -298,46 +325,14 @@ __global__ void __launch_bounds__(256) xgmi_repl_kernel(XgmiTable T, XgmiLaunch 
       __hip_atomic_store(T.flags[tid] + ck_idx(b, me, j, par), t, __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_SYSTEM);
   }
-  drain_vm();
-  __syncthreads();
-  if (tid < W && tid != me) flag_store(T.flags[tid] + arrive_idx(b, me, j), a.epoch);
+  publish(T, tid < W && tid != me, tid, xg_arrive_idx(b, me, j), a.epoch);
 
-  // ---- phase 2: all peers' slices are here (failed wait: no update, as in xgmi_ps_kernel)
-  if (tid == 0) arrived = 1;
-  __syncthreads();
-  if (tid < W && tid != me &&
-      !wait_ge(myflags + arrive_idx(b, tid, j), a.epoch, deadline, a.err, 1))
-    arrived = 0;
-  __syncthreads();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  if (a.check && arrived) {
-    bool ok = true;
-    for (int q = 0; q < W; ++q)
-      if (q != me)
-        ok &= check_piece(slot(me, q), 0, n4, myflags + ck_idx(b, q, j, par), a.err, red);
-    if (!ok && tid == 0) arrived = 0;
-    __syncthreads();
-  }
-  const int n4u = arrived ? n4 : 0;
-  float4* m4 = reinterpret_cast<float4*>(a.m + s0);
-  float4* v4 = a.v ? reinterpret_cast<float4*>(a.v + s0) : nullptr;
-  float4* w4 = reinterpret_cast<float4*>(T.params[me] + a.lo + s0);
-  for (int i = tid; i < n4u; i += 256) {
-    float4 x[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-      if (q < W)
-        x[q] = q == me ? (a.coef != 1.f ? scale4(own[i], a.coef) : own[i])
-                       : ld4_sys(slot(me, q), i * 16);
-    float4 g = f4zero();
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)  // rank order, as the owner kernel: identical bits
-      if (q < W) { g.x += x[q].x; g.y += x[q].y; g.z += x[q].z; g.w += x[q].w; }
-    float4 w = w4[i];
-    upd4_any(a.rule, a.step, w, g, m4, v4, i);
-    w4[i] = w;  // this rank's copy only (the next forward is a later kernel of this stream)
-  }
-  if (a.final_wait) final_wait(a, myflags, W, deadline);
+  // ---- phase 2: the whole slice, from every peer's parity slot, to my copy
+  auto piece = [&](int q) { return Piece{slot(me, q), 0}; };
+  wait_arrivals(a, g);
+  verify_pieces(a, g, par, n4, piece);
+  reduce_update<NQ, false>(T, a, g, piece, a.lo + s0, s0, n4);
+  if (a.final_wait) xg_final_wait(a, myflags, W, deadline);
 }
 
 // One OWNER bucket: a tensor-granular plan's exchange unit — the ranges of
@@ -366,24 +361,24 @@ __global__ void __launch_bounds__(256) xgmi_owner_kernel(XgmiTable T, XgmiLaunch
 #pragma unroll
   for (int k = 1; k < kXgmiMaxRuns; ++k)
     if (k < a.nruns && j >= a.run_sl0[k]) r = k;
-  const int64_t s0 = (int64_t)(j - a.run_sl0[r]) * a.run_slice[r];
-  const int64_t s1 = s0 + a.run_slice[r] < a.run_n[r] ? s0 + a.run_slice[r] : a.run_n[r];
-  const int n4 = s0 < s1 ? (int)((s1 - s0) >> 2) : 0;
-  const int64_t lo = a.run_lo[r] + s0;    // plan-buffer offset of the slice
-  const int64_t vo = a.run_voff[r] + s0;  // its offset in the unit's inbox slot
+  const XgSlice s = xg_slice(j - a.run_sl0[r], a.run_slice[r], a.run_n[r]);
+  const int n4 = s.n4;
+  const int64_t lo = a.run_lo[r] + s.s0;    // plan-buffer offset of the slice
+  const int64_t vo = a.run_voff[r] + s.s0;  // its offset in the unit's inbox slot
   uint32_t* myflags = T.flags[me];
   __shared__ uint32_t red[4];
   __shared__ int arrived;
-  const float4* mine = reinterpret_cast<const float4*>(a.grads + lo);
+  const Round g{W, me, b, j, deadline, myflags, red, &arrived};
 
   if (me != own) {
+    const float4* mine = reinterpret_cast<const float4*>(a.grads + lo);
     const brsrc_t dst = make_rsrc(T.inbox[own] + a.inbox_off + (int64_t)me * a.c + vo,
                                   (uint32_t)n4 * 16u);
     uint32_t cs = 0;
     for (int i = tid; i < n4; i += 256) {
       const float4 x = mine[i];
       const float4 v = a.coef != 1.f ? scale4(x, a.coef) : x;
-      st4_sys(dst, i * 16, v);
+      bstore4_sys(dst, i * 16, v);
       if (a.check) cs += bits4(v);
     }
     if (a.check) {  // the slice's checksum at the owner, before the ARRIVE word (same drain)
@@ -392,59 +387,19 @@ __global__ void __launch_bounds__(256) xgmi_owner_kernel(XgmiTable T, XgmiLaunch
         __hip_atomic_store(T.flags[own] + ck_idx(b, me, j), t, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    drain_vm();
-    __syncthreads();
-    if (tid == 0) flag_store(T.flags[own] + arrive_idx(b, me, j), a.epoch);
-    if (a.final_wait) final_wait(a, myflags, W, deadline);
+    publish(T, tid == 0, own, xg_arrive_idx(b, me, j), a.epoch);
+    if (a.final_wait) xg_final_wait(a, myflags, W, deadline);
     return;
   }
 
-  if (tid == 0) arrived = 1;
-  __syncthreads();
-  if (tid < W && tid != me &&
-      !wait_ge(myflags + arrive_idx(b, tid, j), a.epoch, deadline, a.err, 1))
-    arrived = 0;  // (no update on a failed wait: see xgmi_ps_kernel)
-  __syncthreads();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  // the owner: the unit's slice, from every peer's slot [q] of my inbox, to every rank
   const brsrc_t inbox = make_rsrc(T.inbox[me] + a.inbox_off, (uint32_t)(W * a.c * 4));
-  if (a.check && arrived) {  // every pusher's slice against its published checksum
-    bool ok = true;
-    for (int q = 0; q < W; ++q)
-      if (q != me)
-        ok &= check_piece(inbox, (int)(((int64_t)q * a.c + vo) * 4), n4,
-                          myflags + ck_idx(b, q, j), a.err, red);
-    if (!ok && tid == 0) arrived = 0;
-    __syncthreads();
-  }
-  const int n4u = arrived ? n4 : 0;
-  float4* m4 = a.m ? reinterpret_cast<float4*>(a.m + a.run_soff[r] + s0) : nullptr;
-  float4* v4 = a.v ? reinterpret_cast<float4*>(a.v + a.run_soff[r] + s0) : nullptr;
-  float4* w4 = reinterpret_cast<float4*>(T.params[me] + lo);
-  for (int i = tid; i < n4u; i += 256) {
-    float4 x[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-      if (q < W)
-        x[q] = q == me ? (a.coef != 1.f ? scale4(mine[i], a.coef) : mine[i])
-                       : ld4_sys(inbox, (int)(((int64_t)q * a.c + vo) * 4) + i * 16);
-    float4 w = w4[i];
-    float4 g = f4zero();
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)  // rank order, as the RCCL reduce and xgmi_ps_kernel
-      if (q < W) { g.x += x[q].x; g.y += x[q].y; g.z += x[q].z; g.w += x[q].w; }
-    upd4_any(a.rule, a.step, w, g, m4, v4, i);
-#pragma unroll
-    for (int k = 0; k < NQ; ++k) {
-      if (k < W) {
-        const int q = (me + k + j) % W;
-        st4_sys(make_rsrc(T.params[q] + lo, (uint32_t)n4 * 16u), i * 16, w);
-      }
-    }
-  }
-  drain_vm();
-  __syncthreads();
-  if (tid < W) flag_store(T.flags[tid] + done_idx(b, me, j), a.epoch);
-  if (a.final_wait) final_wait(a, myflags, W, deadline);
+  auto piece = [&](int q) { return Piece{inbox, (int)(((int64_t)q * a.c + vo) * 4)}; };
+  wait_arrivals(a, g);
+  verify_pieces(a, g, 0, n4, piece);
+  reduce_update<NQ, true>(T, a, g, piece, lo, a.run_soff[r] + s.s0, n4);
+  publish(T, tid < W, tid, xg_done_idx(b, me, j), a.epoch);
+  if (a.final_wait) xg_final_wait(a, myflags, W, deadline);
 }
 
 #define X_CHECK(x)                                                                        \
@@ -574,95 +529,26 @@ PeerExchange::PeerExchange(float* params, const float* grads, int64_t total, int
                            int repl_bucket)
     : repl_(repl_bucket), params_(params), grads_(grads), total_(total), world_(world),
       rank_(rank), map_("xgmi", params, world, rank, 20.0) {
-  if (world < 1 || world > kXgmiMaxPeers) throw std::invalid_argument("xgmi: world out of range");
-  if (rank < 0 || rank >= world) throw std::invalid_argument("xgmi: rank out of range");
-  if (buckets.empty() || (int)buckets.size() > kXgmiMaxBuckets)
-    throw std::invalid_argument("xgmi: 1..32 buckets");
-  if (max_slices < 1 || max_slices > kXgmiMaxSlices)
-    throw std::invalid_argument("xgmi: max_slices out of range");
   if (reinterpret_cast<uintptr_t>(params) % 16 || reinterpret_cast<uintptr_t>(grads) % 16)
     throw std::invalid_argument("xgmi: buffers must be 16-B aligned");
-  if (repl_bucket >= (int)buckets.size()) throw std::invalid_argument("xgmi: replicated bucket");
   init(buckets, max_slices);
 }
 
+// The plan (xgmi_plan.h: refusals, slices, inbox offsets), then what needs HIP.  The records are
+// finished last: the error word exists only after alloc.
 void PeerExchange::init(const std::vector<XgmiBucketSpec>& buckets, int max_slices) {
-  const int world = world_;
-  int64_t inbox = 0;
-  for (size_t bi = 0; bi < buckets.size(); ++bi) {
-    const XgmiBucketSpec& sp = buckets[bi];
-    const bool repl = (int)bi == repl_;
-    Bucket B;
-    B.owner = sp.owner;
-    B.inbox_off = inbox;
-    if (sp.owner >= 0) {
-      // owner bucket: the runs concatenated; each run sliced on its own (a slice never crosses
-      // a run), >= 1024 elements per slice, at most max_slices slices over the whole unit
-      if (sp.owner >= world) throw std::invalid_argument("xgmi: bucket owner out of range");
-      if (repl) throw std::invalid_argument("xgmi: an owner bucket cannot be replicated");
-      if (sp.runs.empty() || (int)sp.runs.size() > kXgmiMaxRuns ||
-          sp.state_offs.size() != sp.runs.size())
-        throw std::invalid_argument("xgmi: owner bucket needs 1..8 runs with state offsets");
-      int64_t n = 0;
-      for (size_t r = 0; r < sp.runs.size(); ++r) {
-        const int64_t lo = sp.runs[r].first, hi = sp.runs[r].second;
-        if (lo < 0 || hi > total_ || hi <= lo || (hi - lo) % 4 || lo % 4 || sp.state_offs[r] % 4 ||
-            sp.state_offs[r] < 0)
-          throw std::invalid_argument("xgmi: owner-bucket run out of range or not 16-B shaped");
-        n += hi - lo;
-      }
-      int64_t ns = (n + 1023) / 1024;
-      if (ns > max_slices) ns = max_slices;
-      if (ns < (int64_t)sp.runs.size()) ns = (int64_t)sp.runs.size();
-      const int64_t per = ((n + ns - 1) / ns + 3) & ~(int64_t)3;
-      int sl = 0;
-      int64_t voff = 0;
-      for (size_t r = 0; r < sp.runs.size(); ++r) {
-        const int64_t rn = sp.runs[r].second - sp.runs[r].first;
-        B.run_lo.push_back(sp.runs[r].first);
-        B.run_n.push_back(rn);
-        B.run_soff.push_back(sp.state_offs[r]);
-        B.run_voff.push_back(voff);
-        B.run_slice.push_back(per);
-        B.run_sl0.push_back(sl);
-        sl += (int)((rn + per - 1) / per);
-        voff += rn;
-      }
-      B.run_sl0.push_back(sl);
-      if (sl > kXgmiMaxSlices) throw std::invalid_argument("xgmi: owner bucket has too many slices");
-      B.lo = sp.runs[0].first;
-      B.c = n;
-      B.slice = per;
-      B.nslice = sl;
-      if (n * 4 * world > 0x7fffffffLL) throw std::invalid_argument("xgmi: bucket too large");
-      inbox += n * world;
-      bk_.push_back(B);
-      continue;
-    }
-    if (sp.runs.size() != 1) throw std::invalid_argument("xgmi: equal-chunk bucket needs one range");
-    const int64_t lo = sp.runs[0].first, hi = sp.runs[0].second;
-    if (lo < 0 || hi > total_ || hi <= lo) throw std::invalid_argument("xgmi: bucket out of range");
-    if ((hi - lo) % (repl ? 4 : 4 * world))
-      throw std::invalid_argument("xgmi: bucket not divisible by 4W (replicated: by 4)");
-    B.lo = lo;
-    // owner buckets: this rank's chunk; the replicated bucket: all of it
-    B.c = repl ? hi - lo : (hi - lo) / world;
-    // >= 1024 elements (4 KB) per workgroup slice, at most max_slices workgroups
-    int64_t ns = (B.c + 1023) / 1024;
-    if (ns > max_slices) ns = max_slices;
-    if (ns < 1) ns = 1;
-    B.slice = ((B.c + ns - 1) / ns + 3) & ~(int64_t)3;
-    B.nslice = (int)((B.c + B.slice - 1) / B.slice);
-    B.slot = B.c;
-    if (B.slot * 4 * world * (repl ? 2 : 1) > 0x7fffffffLL)
-      throw std::invalid_argument("xgmi: bucket too large");
-    inbox += B.slot * world * (repl ? 2 : 1);  // replicated: two parity slots per source
-    bk_.push_back(B);
-  }
+  XgmiPlan plan = plan_buckets(buckets, total_, world_, rank_, max_slices, repl_);
   // ARRIVE, DONE and (check mode) checksum words, the replicated bucket's in two parities
-  map_.alloc(inbox, 4ull * kXgmiMaxBuckets * kXgmiMaxPeers * kXgmiMaxSlices * sizeof(uint32_t));
+  map_.alloc(plan.inbox, 4ull * kXgmiMaxBuckets * kXgmiMaxPeers * kXgmiMaxSlices * sizeof(uint32_t));
   X_CHECK(hipDeviceSynchronize());
   check_ = env_flag("DDL_XGMI_CHECK", false, /*only_1=*/true);
+  bk_ = std::move(plan.rec);
+  for (XgmiLaunch& a : bk_) {
+    a.grads = grads_;
+    a.err = map_.err;
+    a.timeout_ticks = map_.timeout_ticks();
+    a.check = check_ ? 1 : 0;
+  }
 }
 
 PeerExchange::~PeerExchange() { close(); }
@@ -671,86 +557,42 @@ void PeerExchange::fill(int bucket, uint32_t epoch, const XgmiUpdate& u, bool fi
                         bool gated, XgmiLaunch& a) const {
   if (!map_.opened) throw std::runtime_error("xgmi: open() the peer handles first");
   if (bucket < 0 || bucket >= (int)bk_.size()) throw std::invalid_argument("xgmi: bucket index");
-  const Bucket& B = bk_[bucket];
-  const bool owns = B.owner < 0 || B.owner == rank_;  // runs the update of (part of) the bucket
+  const bool owns = owner(bucket) < 0 || owner(bucket) == rank_;  // runs (part of) the update
   if (owns && u.rule.kind != kUpdCopy && !u.m)
     throw std::invalid_argument("xgmi: optimizer state missing");
   if (owns && u.rule.kind == kUpdAdam && !u.v) throw std::invalid_argument("xgmi: Adam needs v");
-  memset(&a, 0, sizeof(a));
-  a.world = world_;
-  a.rank = rank_;
-  a.bucket = bucket;
-  a.nbuckets = (int)bk_.size();
+  a = bk_[bucket];
   a.final_wait = final_wait ? 1 : 0;
   a.epoch = epoch;
-  a.lo = B.lo;
-  a.c = B.c;
-  a.inbox_off = B.inbox_off;
-  a.slice = B.slice;
-  a.rslot = B.slot;
-  for (size_t i = 0; i < bk_.size(); ++i) a.nslices[i] = bk_[i].nslice;
-  a.grads = grads_;
   a.m = u.m;
   a.v = u.v;
   a.rule = u.rule;
   a.step = u.step;
   a.coef = u.coef;
-  a.err = map_.err;
-  a.timeout_ticks = map_.timeout_ticks();
-  a.check = check_ ? 1 : 0;
-  a.repl_bucket = repl_;
   a.gate_err = gated ? gate_err_ : nullptr;
-  for (size_t i = 0; i < bk_.size(); ++i) a.owners[i] = bk_[i].owner;
-  for (int i = (int)bk_.size(); i < kXgmiMaxBuckets; ++i) a.owners[i] = -1;
-  if (B.owner >= 0) {
-    a.owner = B.owner;
-    a.nruns = (int)B.run_lo.size();
-    for (int r = 0; r < a.nruns; ++r) {
-      a.run_lo[r] = B.run_lo[r];
-      a.run_n[r] = B.run_n[r];
-      a.run_soff[r] = B.run_soff[r];
-      a.run_voff[r] = B.run_voff[r];
-      a.run_slice[r] = B.run_slice[r];
-      a.run_sl0[r] = B.run_sl0[r];
-    }
-    a.run_sl0[a.nruns] = B.run_sl0[a.nruns];
-  }
+}
+
+// The kernel of a bucket family (0 owner, 1 replicated, 2 equal-chunk) with its rank loops
+// unrolled for world size N (0: any).  Only the owner family has a <1> form.
+using XgmiKernel = void (*)(XgmiTable, XgmiLaunch);
+template <int N>
+static XgmiKernel bucket_kernel(int family) {
+  constexpr int M = N == 1 ? 0 : N;
+  return family == 0 ? xgmi_owner_kernel<N> : family == 1 ? xgmi_repl_kernel<M> : xgmi_ps_kernel<M>;
 }
 
 void PeerExchange::launch(int bucket, uint32_t epoch, const XgmiUpdate& u, bool final_wait,
                           hipStream_t st, bool gated) {
   XgmiLaunch a;
   fill(bucket, epoch, u, final_wait, gated, a);
-  const Bucket& B = bk_[bucket];
-  if (B.owner >= 0) {
-    switch (world_) {
-#define X_CASE(N) \
-  case N: DDL_LAUNCH(xgmi_owner_kernel<N>, dim3(B.nslice), dim3(256), 0, st, map_.table, a); break;
-      X_CASE(1) X_CASE(2) X_CASE(3) X_CASE(4) X_CASE(5) X_CASE(6) X_CASE(7) X_CASE(8)
-#undef X_CASE
-      default: DDL_LAUNCH(xgmi_owner_kernel<0>, dim3(B.nslice), dim3(256), 0, st, map_.table, a);
-    }
-    DDL_CHECK_LAUNCH();
-    return;
-  }
-  if (bucket == repl_) {
-    switch (world_) {
-#define X_CASE(N) \
-  case N: DDL_LAUNCH(xgmi_repl_kernel<N>, dim3(B.nslice), dim3(256), 0, st, map_.table, a); break;
-      X_CASE(2) X_CASE(3) X_CASE(4) X_CASE(5) X_CASE(6) X_CASE(7) X_CASE(8)
-#undef X_CASE
-      default: DDL_LAUNCH(xgmi_repl_kernel<0>, dim3(B.nslice), dim3(256), 0, st, map_.table, a);
-    }
-    DDL_CHECK_LAUNCH();
-    return;
-  }
+  const int family = owner(bucket) >= 0 ? 0 : bucket == repl_ ? 1 : 2;
+  XgmiKernel k = bucket_kernel<0>(family);
   switch (world_) {
-#define X_CASE(N) \
-  case N: DDL_LAUNCH(xgmi_ps_kernel<N>, dim3(B.nslice), dim3(256), 0, st, map_.table, a); break;
-    X_CASE(2) X_CASE(3) X_CASE(4) X_CASE(5) X_CASE(6) X_CASE(7) X_CASE(8)
+#define X_CASE(N) case N: k = bucket_kernel<N>(family); break;
+    X_CASE(1) X_CASE(2) X_CASE(3) X_CASE(4) X_CASE(5) X_CASE(6) X_CASE(7) X_CASE(8)
 #undef X_CASE
-    default: DDL_LAUNCH(xgmi_ps_kernel<0>, dim3(B.nslice), dim3(256), 0, st, map_.table, a);
   }
+  DDL_LAUNCH(k, dim3(nslices(bucket)), dim3(256), 0, st, map_.table, a);
   DDL_CHECK_LAUNCH();
 }
 

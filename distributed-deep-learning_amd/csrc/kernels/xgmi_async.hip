@@ -60,39 +60,11 @@
 #include "api.h"
 #include "trace.h"
 #include "common.h"
+#include "xgmi_dev.h"
 
 namespace ddl {
 
 namespace {
-
-DDL_DEV void drain_vm() { drain_vmem(); }
-
-DDL_DEV bool wait_ge(const uint32_t* f, uint32_t target, long long deadline, int* err, int code) {
-  // the error word lives in host memory (a PCIe round trip per load): look at it, and at the
-  // clock, only every 32nd poll, so a flag that lands is seen within one poll of local memory
-  for (int it = 0; (int32_t)(__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) - target) < 0; ++it) {
-    if ((it & 31) == 31) {
-      if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0) return false;
-      if (wall_clock64() > deadline) {
-        __hip_atomic_store(err, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        return false;
-      }
-    }
-    __builtin_amdgcn_s_sleep(2);
-  }
-  return true;
-}
-// The flag that publishes a workgroup's payload.  Every payload store is a system-scope
-// (sc0|sc1) write-through store, and every storing wave drains vmcnt(0) before the workgroup
-// barrier that precedes the flag store: a write-through store is counted complete only once the
-// memory side (local HBM, or the peer over xGMI, or host memory) has acknowledged it, so the
-// payload is globally visible before the flag is issued — no L2 write-back is needed (the CDNA
-// guide's G16 write-through hand-off, at system scope).  A full system release at each flag (L2
-// write-back + wait) writes back every dirty line of the XCD's L2 — the GEMMs' output included —
-// and measured 3.2 -> 5.4 ms/step on the two-ranks-on-one-GPU rehearsal (round 2).
-DDL_DEV void flag_store(uint32_t* f, uint32_t v) {
-  __hip_atomic_store(f, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 
 // completion words DONE[worker][ps][slice] in the shared host segment, then the arrival board
 // POSTED[ps][worker][slice].  Every word has ONE writer and is only stored, never
@@ -139,9 +111,9 @@ __global__ void __launch_bounds__(256) async_push_kernel(const AsyncTable* __res
   const int p = a.subset ? a.ps[e] : e;
   const AsyncShard& S = T.shard[p];
   const int j = blk - a.first_blk[e];
-  const int64_t s0 = (int64_t)j * S.slice;
-  const int64_t s1 = s0 + S.slice < S.n ? s0 + S.slice : S.n;
-  const int n4 = s0 < s1 ? (int)((s1 - s0) >> 2) : 0;
+  const XgSlice sl = xg_slice(j, S.slice, S.n);
+  const int64_t s0 = sl.s0;
+  const int n4 = sl.n4;
   const float4* src = reinterpret_cast<const float4*>(a.grads + S.lo + s0);
   const brsrc_t dst = make_rsrc(T.inbox[S.host] + S.inbox_off + (int64_t)a.rank * S.n + s0,
                                 (uint32_t)n4 * 16u);
@@ -151,7 +123,7 @@ __global__ void __launch_bounds__(256) async_push_kernel(const AsyncTable* __res
     if (a.coef != 1.f) { x.x *= a.coef; x.y *= a.coef; x.z *= a.coef; x.w *= a.coef; }
     bstore4_sys(dst, i * 16, x);
   }
-  drain_vm();
+  drain_vmem();
   __syncthreads();
   if (tid == 0) {
     __hip_atomic_store(T.posted + posted_word(p, a.rank, j), a.epoch, __ATOMIC_RELAXED,
@@ -176,9 +148,9 @@ struct ApplyArgs {
 DDL_DEV void apply_body(const AsyncTable& T, const ApplyArgs& a, int j) {
   const AsyncShard& S = T.shard[a.ps];
   const int tid = threadIdx.x;
-  const int64_t s0 = (int64_t)j * S.slice;
-  const int64_t s1 = s0 + S.slice < S.n ? s0 + S.slice : S.n;
-  const int n4 = s0 < s1 ? (int)((s1 - s0) >> 2) : 0;
+  const XgSlice sl = xg_slice(j, S.slice, S.n);
+  const int64_t s0 = sl.s0;
+  const int n4 = sl.n4;
   const float* src = T.elide && a.worker == a.me
                         ? T.grads + S.lo + s0  // this rank's own push: no inbox copy
                         : T.inbox[a.me] + S.inbox_off + (int64_t)a.worker * S.n + s0;
@@ -194,11 +166,11 @@ DDL_DEV void apply_body(const AsyncTable& T, const ApplyArgs& a, int j) {
     w4[i] = w;
     bstore4_sys(out, i * 16, w);
   }
-  drain_vm();
+  drain_vmem();
   __syncthreads();
   if (tid == 0) {
-    flag_store(T.flags[a.worker] + done_dev_idx(S, j), a.epoch);  // the worker's gate
-    flag_store(T.done + done_word(a.worker, a.ps, j), a.epoch);       // the worker's host
+    xg_flag_store(T.flags[a.worker] + done_dev_idx(S, j), a.epoch);  // the worker's gate
+    xg_flag_store(T.done + done_word(a.worker, a.ps, j), a.epoch);   // the worker's host
   }
 }
 
@@ -284,47 +256,15 @@ AsyncPeer::AsyncPeer(float* params, const float* grads, int64_t total, int world
                      const std::vector<int>& ps_host, int max_slices)
     : params_(params), grads_(grads), world_(world), rank_(rank),
       map_("xgmi-async", params, world, rank, 60.0) {
-  if (world < 1 || world > kXgmiMaxPeers) throw std::invalid_argument("async xgmi: world");
-  if (rank < 0 || rank >= world) throw std::invalid_argument("async xgmi: rank");
-  if (ps_ranges.empty() || (int)ps_ranges.size() > kAsyncMaxPs ||
-      ps_ranges.size() != ps_host.size())
-    throw std::invalid_argument("async xgmi: 1..64 PS, one host each");
-  if (max_slices < 1 || max_slices > kAsyncMaxSlices)
-    throw std::invalid_argument("async xgmi: max_slices");
   if (reinterpret_cast<uintptr_t>(params) % 16 || reinterpret_cast<uintptr_t>(grads) % 16)
     throw std::invalid_argument("async xgmi: buffers must be 16-B aligned");
+  // every shard's slices and every host's inbox layout: xgmi_plan.h
+  const AsyncPlan plan = plan_async_shards(ps_ranges, ps_host, total, world, rank, max_slices);
   memset(&table_, 0, sizeof(table_));
-  nps_ = (int)ps_ranges.size();
-  int64_t inbox = 0;
-  for (int p = 0; p < nps_; ++p) {
-    AsyncShard& S = table_.shard[p];
-    S.lo = ps_ranges[p].first;
-    S.n = ps_ranges[p].second - ps_ranges[p].first;
-    S.host = ps_host[p];
-    if (S.lo < 0 || S.n <= 0 || S.lo + S.n > total || S.n % 4 || S.lo % 4)
-      throw std::invalid_argument("async xgmi: PS range must be a 4-aligned slice of the buffer");
-    if (S.host < 0 || S.host >= world) throw std::invalid_argument("async xgmi: PS host");
-    // >= 2048 elements (8 KB) per workgroup, at most max_slices workgroups: a 1.6 M-element
-    // shard spreads over 512 workgroups (64 left the apply at ~2 TB/s, 41.6 us for the whole
-    // model at W = 1, profiles/r4_step_timeline_async_xgmi_w1.txt)
-    int64_t ns = (S.n + 2047) / 2048;
-    if (ns > max_slices) ns = max_slices;
-    S.slice = ((S.n + ns - 1) / ns + 3) & ~(int64_t)3;
-    S.nslice = (int)((S.n + S.slice - 1) / S.slice);
-    S.slice0 = p == 0 ? 0 : table_.shard[p - 1].slice0 + table_.shard[p - 1].nslice;
-    if (S.n * 4 * world > 0x7fffffffLL) throw std::invalid_argument("async xgmi: shard too large");
-  }
-  // inbox of a host: one [W][n] slot block per hosted PS, in PS order (every rank computes
-  // every host's layout identically, so pushes know where to write)
-  std::vector<int64_t> off(world, 0);
-  for (int p = 0; p < nps_; ++p) {
-    AsyncShard& S = table_.shard[p];
-    S.inbox_off = off[S.host];
-    off[S.host] += S.n * world;
-  }
-  inbox = off[rank];
+  nps_ = (int)plan.shard.size();
+  std::copy(plan.shard.begin(), plan.shard.end(), table_.shard);
   // the flags: DONE, then POSTED[worker]
-  map_.alloc(inbox > 0 ? inbox : 4, kAsyncFlagWords * sizeof(uint32_t));
+  map_.alloc(plan.inbox > 0 ? plan.inbox : 4, kAsyncFlagWords * sizeof(uint32_t));
   X_CHECK(hipMalloc(reinterpret_cast<void**>(&table_dev_), sizeof(AsyncTable)));
   X_CHECK(hipDeviceSynchronize());
   const char* el = getenv("DDL_ASYNC_ELIDE_LOCAL");

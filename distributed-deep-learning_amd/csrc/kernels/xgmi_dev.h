@@ -1,5 +1,6 @@
-// Device side of the xGMI peer-memory flag protocol (xgmi.hip header comment): flag stores,
-// bounded waits and the final DONE wait of the bucket kernels.
+// Device side of the xGMI peer-memory flag protocol (xgmi.hip header comment), the one home of
+// its primitives for xgmi.hip and xgmi_async.hip: the slice a workgroup owns, flag stores, bounded
+// waits and the final DONE wait of the bucket kernels.
 #pragma once
 #include "api.h"
 #include "common.h"
@@ -14,6 +15,18 @@ namespace ddl {
 // guide's G16 write-through hand-off, at system scope).  A full system release at each flag (L2
 // write-back + wait) writes back every dirty line of the XCD's L2 — the GEMMs' output included —
 // and measured 3.2 -> 5.4 ms/step on the two-ranks-on-one-GPU rehearsal (round 2).
+
+// Workgroup j's slice of n floats cut into `slice`-float pieces (xgmi_plan.h slice_geo): its first
+// float and its float4 count (0 past the end).
+struct XgSlice {
+  int64_t s0;
+  int n4;
+};
+DDL_DEV XgSlice xg_slice(int j, int64_t slice, int64_t n) {
+  const int64_t s0 = (int64_t)j * slice;
+  const int64_t s1 = s0 + slice < n ? s0 + slice : n;
+  return {s0, s0 < s1 ? (int)((s1 - s0) >> 2) : 0};
+}
 
 DDL_DEV uint32_t xg_flag_load(const uint32_t* f) {
   return __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -56,11 +69,12 @@ DDL_DEV bool xg_wait_ge(const uint32_t* f, uint32_t target, long long deadline, 
 }
 
 // The final wait of a step: every (bucket, owner, slice) DONE word of the step, except the
-// replicated bucket's (it has none), spread over threads [t0, t0 + nt) of the launch (thread t
-// polls words t - t0, t - t0 + nt, ...) and polled at once.  An owner bucket's DONE words come
-// from its one owner, an equal-chunk bucket's from every rank.
-DDL_DEV void xg_final_wait(const XgmiLaunch& a, uint32_t epoch, const uint32_t* myflags, int W,
-                           long long deadline, int t, int nt) {
+// replicated bucket's (it has none), spread over every thread of the launch (thread t of nt polls
+// words t, t + nt, ...) and polled at once.  An owner bucket's DONE words come from its one
+// owner, an equal-chunk bucket's from every rank.
+DDL_DEV void xg_final_wait(const XgmiLaunch& a, const uint32_t* myflags, int W,
+                           long long deadline) {
+  const int t = blockIdx.x * 256 + threadIdx.x, nt = gridDim.x * 256;
   auto words = [&](int bb) {
     return bb == a.repl_bucket ? 0 : (a.owners[bb] >= 0 ? 1 : W) * a.nslices[bb];
   };
@@ -75,7 +89,7 @@ DDL_DEV void xg_final_wait(const XgmiLaunch& a, uint32_t epoch, const uint32_t* 
       ++bb;
     }
     const int q = x / a.nslices[bb], jj = x - q * a.nslices[bb];
-    xg_wait_ge(myflags + xg_done_idx(bb, a.owners[bb] >= 0 ? a.owners[bb] : q, jj), epoch,
+    xg_wait_ge(myflags + xg_done_idx(bb, a.owners[bb] >= 0 ? a.owners[bb] : q, jj), a.epoch,
                deadline, a.err, 2);
   }
 }

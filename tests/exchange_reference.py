@@ -85,7 +85,7 @@ def rule_step(kind, w, m, v, g, step, mu=0.0, scale=1.0, b1=B1, b2=B2, eps=EPS):
     return w - step * m2 / (v2.sqrt() + eps), m2, v2
 
 
-# ---- geometry: the host arithmetic of PeerExchange::init and AsyncPeer's constructor ------------
+# ---- geometry: the host arithmetic of xgmi_plan.h (PeerExchange, AsyncPeer) ---------------------
 def equal_slices(c, max_slices=128, per_wg=1024):
     """Float4 counts of the workgroup slices of a chunk of c floats."""
     ns = max(1, min((c + per_wg - 1) // per_wg, max_slices))
