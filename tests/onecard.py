@@ -1,7 +1,7 @@
 """One harness for the multi-process GPU tests that put W ranks on ONE card (helper module, not a
 conftest): the rendezvous preamble, the rank launcher with its deadline, the rank wrapper, the
 shared xGMI rank bodies, the one-process PS simulation, the replay set-up, the W = 1 placement
-runs and the small comparison helpers.
+runs, the records of the checkpoint / resume tests and the small comparison helpers.
 
 W worker processes share one GPU (default process group over gloo, ``DDL_DIST_BACKEND``): RCCL
 refuses two ranks on one device, but the xGMI exchange only needs IPC-mapped memory, so the whole
@@ -376,12 +376,13 @@ def simulate_sync(world, steps, batch, dataset, plan, grad_hook=None, update=Non
 
 
 # ---- 6. the replay of an asynchronous run --------------------------------------------------------
-def replay_async(recs, world, order, steps, grad_hook=None, update=None):
+def replay_async(recs, world, order, steps, grad_hook=None, update=None, dataset=None):
     """The run of `recs` (async_rank_record, one per rank) again in this process, in the recorded
     apply `order`: gradients from the HIP engine on the worker's batch and dropout seed
     (grad_hook(ge, r, s), default plain_grad), updates from ops.update_flat on the PS range with
     the step size of the PS's own t (update(st, g, t, h, cfg), default the run's optimizer with
-    no further option).  Returns async_replay.replay's (worker buffers, PS states)."""
+    no further option).  dataset: the ranks' dataset on the card (default
+    dataset_on_card(2000, 500)).  Returns async_replay.replay's (worker buffers, PS states)."""
     import torch
     import async_replay as ar
     from ddl_amd.ops import native
@@ -389,7 +390,7 @@ def replay_async(recs, world, order, steps, grad_hook=None, update=None):
     dev = torch.device("cuda", 0)
     cfg = recs[0]["cfg"]
     ge = GradEngine(recs[0]["total"], recs[0]["offsets"], cfg["batch_size"],
-                    dataset_on_card(2000, 500), world, cfg)
+                    dataset if dataset is not None else dataset_on_card(2000, 500), world, cfg)
     # the xGMI service holds lr and the betas as float32 and widens them for the step size
     # (update.h adam_step_size; tests/test_numerics_cpu.py pins that to adam_coeffs on the same
     # operands); a decay is formed from the doubles (update.h upd_decay)
@@ -516,18 +517,88 @@ def placement_run(data, opts, shard, steps, batch, tail=None, final=None, setup=
     return out
 
 
-def assert_same_run(a, b, has_v=None):
-    """Two placement_run results: the same parameters, m and v (has_v: whether the rule keeps one)."""
+def assert_same_run(a, b, has_v=None, t=None):
+    """Two placement_run (or run_state) results: the same parameters, m and v (has_v: whether the
+    rule keeps one).  t: every server's state is (m, v, t) and both runs' counters equal `t`."""
     import torch
     from oracle_common import bits
     (pa, sa, _), (pb, sb, _) = a, b
     assert torch.isfinite(pa).all()
-    assert torch.equal(pa, pb) and torch.equal(bits(pa), bits(pb))
+    assert torch.equal(pa, pb) and torch.equal(bits(pa), bits(pb)), "parameters differ"
     assert len(sa) == len(sb) > 0
-    for (ma, va), (mb, vb) in zip(sa, sb):
-        assert torch.equal(ma, mb) and torch.equal(bits(ma), bits(mb))
+    for p, (xa, xb) in enumerate(zip(sa, sb)):
+        (ma, va), (mb, vb) = xa[:2], xb[:2]
+        if t is not None:
+            assert xa[2] == xb[2] == t, f"PS {p}: t {xa[2]} and {xb[2]}, expected {t}"
+        assert torch.equal(ma, mb) and torch.equal(bits(ma), bits(mb)), f"PS {p}: m differs"
         assert (va is None) == (vb is None)
         if has_v is not None:
             assert (va is not None) == has_v
         if va is not None:
-            assert torch.equal(va, vb) and torch.equal(bits(va), bits(vb))
+            assert torch.equal(va, vb) and torch.equal(bits(va), bits(vb)), f"PS {p}: v differs"
+
+
+# ---- 8. checkpoint and resume --------------------------------------------------------------------
+def run_state(tr):
+    """A trained Trainer's state in placement_run's form, with the step counters: the parameters
+    and every server's (m, v, t), after the exchange has written the optimizer state it holds
+    itself back into the PS objects (sync_ps_state)."""
+    import torch
+    torch.cuda.synchronize()
+    tr.exchange.sync_ps_state()
+    torch.cuda.synchronize()
+    state = [(s.m.clone(), None if s.v is None else s.v.clone(), s.t)
+             for _, s in sorted(tr.servers.items())]
+    return tr.params.clone(), state, None
+
+
+def ps_flat(tr, name):
+    """The hosted servers' `name` ("m", "v") laid out as the plan's flat buffer: zeros where this
+    rank hosts nothing, None where the rule keeps no such slot."""
+    import torch
+    out = torch.zeros_like(tr.params)
+    for ps in tr.servers.values():
+        buf = getattr(ps, name)
+        if buf is None:
+            return None
+        for (lo, hi), off in zip(ps.segments, ps.seg_off):
+            out[lo:hi] = buf[off:off + hi - lo]
+    return out
+
+
+def canon_state(tr):
+    """A one-rank Trainer's parameters, m and v in canonical order on the CPU (canon): what a
+    checkpoint must hold whatever the plan.  Reads the PS objects: sync_ps_state() comes first."""
+    offs = tr.plan.tensor_offsets
+    out = {"w": canon(tr.params, offs).cpu()}
+    for name in ("m", "v"):
+        flat = ps_flat(tr, name)
+        out[name] = None if flat is None else canon(flat, offs).cpu()
+    return out
+
+
+def hosted_ps_record(tr):
+    """Every hosted PS's t, m, v and (async) private parameter copy, on the CPU."""
+    return {p: dict(t=s.t, m=s.m.cpu(), v=None if s.v is None else s.v.cpu(),
+                    w=None if s.params is None else s.params.cpu())
+            for p, s in tr.servers.items()}
+
+
+def async_train_record(tr, world):
+    """One asynchronous xGMI rank driven by Trainer.train() (with cfg.resume: checkpoint.load,
+    then exchange.start(); join, verify_provenance, the end-of-run save and close inside): the
+    record async_rank_record returns.  `init` is taken before train(), so a resumed rank's is its
+    fresh initialisation, not the restored buffer; the provenance counts this job's rounds
+    from 0."""
+    import torch
+    ex = tr.exchange
+    init = tr.params.clone()
+    tr.train()
+    torch.cuda.synchronize()
+    P = tr.plan.num_ps
+    return dict(init=init.cpu(), params=tr.params.cpu(), ps=hosted_ps_record(tr),
+                provenance=list(ex.provenance), served=ex.served, steps=tr.global_step,
+                pushes=ex.steps, service_mode=ex.service_mode,
+                ranges=[tr.plan.ps_segments(p)[0] for p in range(P)],
+                hosts=[tr.plan.host_rank(p, world) for p in range(P)],
+                offsets=list(tr.plan.tensor_offsets), total=tr.plan.total, cfg=tr.cfg.to_dict())

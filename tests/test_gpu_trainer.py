@@ -31,6 +31,13 @@ def _trainer(data, **kw):
 
 
 def test_checkpoint_resume_continues_exactly(tmp_path, data):
+    """W = 1, sync, Adam, the contiguous plan, every update local: ``checkpoint.save`` / ``load``
+    called directly around per-step calls.  What it does not cover: any exchange that holds
+    optimizer state of its own (with no collectives ``exchange.repl`` is None, so
+    ``sync_ps_state`` / ``load_ps_state`` return at their first line), momentum / SGD and the
+    update modifiers, clip, accumulation, shuffle, a resume through ``Trainer.train()``, the
+    asynchronous data planes, a changed plan, and anything at W > 1.  Those are
+    tests/test_resume_gpu.py."""
     ref = _trainer(data, steps=12)
     for i in range(12):
         ref.train_step(i)
